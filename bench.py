@@ -3,17 +3,30 @@
 shapes BASELINE.json names, one process per GPU.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload mal|c3|c5|c5shard|ml1m|ml100k] [--double]
+                  [--dump-outputs DIR] [--full]
 
 A "step" is one full ALS iteration = EmfLord.alsTrainIter(): the byUser half-step, the
 exchange of the solved user shard, the byItem half-step and its exchange.  Inputs (CSR by
 user and by item, both factor matrices) are resident in HBM before the timed region.  With
 N > 1 the total problem is fixed and rows are sharded over the ranks ("strong").
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
-  roofline      -- the dominant kernel (per half-step) against the roof that binds it, from HIP-event
-                   durations measured inside libycnr_als.so on the launch stream
+A plain run does what the headline figure needs and no more: set up, warm up, time the K steps,
+write the outputs (--dump-outputs) and print ONE JSON line on rank 0 (metric, value, unit,
+higher_is_better, dtype, ms_per_step, the configuration) with two objects that cost no run of their
+own, both read from the HIP-event durations libycnr_als.so records on its launch stream in the timed steps:
+  roofline      -- the dominant kernel (per half-step) against the roof that binds it
+  exchange      -- where the iteration's time went per half-step
+--full adds what takes passes of its own:
+  rmse_*        -- the in-sample RMSE pass over a 10 % sample of the ratings and its device time (also with
+                   --dump-factors, whose file stores the RMSE)
   cpu_baseline  -- the CPU oracle (a port of the reference algorithm) timed on a bounded row
-                   sample of the same workload on this box's host cores (N = 1 only)
+                   sample of the same workload on the host's cores (N = 1 only), and cpu_baseline_blas
+
+--dump-outputs DIR writes what the last timed step left behind, the two factor matrices a caller of
+EmfLord.alsTrainIter() reads back, as DIR/U.npy and DIR/V.npy (float32, or float64 with --double).  A
+matrix larger than its share of 64 MB is written as a fixed, seeded sample of its rows (the row ids
+are in DIR/U_rows.npy / DIR/V_rows.npy, as float64).  The inputs depend on the arguments alone, so
+two builds of the library can be compared output for output.
 """
 import argparse
 import json
@@ -111,7 +124,13 @@ def main():
     ap.add_argument("--double", action="store_true", help="useDoublePrecision")
     ap.add_argument("--chunk", type=int, default=0, help="ratings per split work unit (0 = library default)")
     ap.add_argument("--factors", type=int, default=0, help="experiments: factorsCount instead of the workload's (the line is then NOT the workload's metric; config.factors says so)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes passes of its own beside the timed steps: the in-sample RMSE pass and the two CPU baselines "
+                         "(a plain run leaves them out)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the factor matrices the last step left to DIR/U.npy and DIR/V.npy "
+                         "(at most 64 MB in all: a fixed, seeded row sample of a larger matrix, its row ids beside it)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baselines out")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only for functional tests)")
     ap.add_argument("--same-device", action="store_true",
@@ -141,6 +160,8 @@ def main():
                     help="timing experiment only: fold all column ids into [0, N) so every gather hits L1/L2")
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="target CPU time of the baseline sample")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -180,11 +201,14 @@ def main():
         by_item.indx %= args.debug_mod_idx
     torch.cuda.synchronize()
     t_gen = time.time() - t0
-    # in-sample RMSE set: every 10th rating of each... keep it simple: a 10 % Bernoulli sample
-    g = torch.Generator(device=dev)
-    g.manual_seed(7)
-    from ycnr_als.data import select_csr
-    val = select_csr(by_user, torch.rand(nnz, generator=g, device=dev) < 0.10)
+    # in-sample RMSE set (--full, and --dump-factors, which stores the RMSE; the half-steps never read it): a 10 % Bernoulli sample
+    val = None
+    want_rmse = args.full or bool(args.dump_factors)
+    if want_rmse:
+        g = torch.Generator(device=dev)
+        g.manual_seed(7)
+        from ycnr_als.data import select_csr
+        val = select_csr(by_user, torch.rand(nnz, generator=g, device=dev) < 0.10)
     ds = Dataset(by_user, by_item, validate=val, test=None, total_ratings_avg=float(by_user.vals.double().mean()))
     requested_transport = args.transport or ("shm" if args.same_device or args.backend == "gloo" else "rccl")
     lord = EmfLord(options={"factorsCount": k, "trainIters": args.steps, "useDoublePrecision": args.double,
@@ -412,19 +436,24 @@ def main():
         if args.transport_ab and args.transport_ab != requested_transport:
             exchange["ab"] = transport_ab(args, dist, ds, k, max_rating, local_rank, dev, barrier, lord.shards)
 
-    rmse = lord.calcRmse("rmseValidate", False)
-    # the RMSE pass BASELINE's metric names beside the solve: device time of its kernel over this rank's users (HIP events inside
-    # libycnr_als.so), max over the ranks
-    rmse_ms = lord.backend.dev.last_rmse_ms() if hasattr(lord.backend, "dev") else None
-    if dist and rmse_ms is not None:
-        t = torch.tensor([rmse_ms], dtype=torch.float64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        rmse_ms = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, lord)
+
+    rmse = rmse_ms = None
+    if want_rmse:
+        rmse = lord.calcRmse("rmseValidate", False)
+        # the RMSE pass BASELINE's metric names beside the solve: device time of its kernel over this rank's users (HIP events inside
+        # libycnr_als.so), max over the ranks
+        rmse_ms = lord.backend.dev.last_rmse_ms() if hasattr(lord.backend, "dev") else None
+        if dist and rmse_ms is not None:
+            t = torch.tensor([rmse_ms], dtype=torch.float64, device=dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            rmse_ms = float(t.item())
     if args.dump_factors and rank == 0:
         np.savez(args.dump_factors, U=lord.backend.get_factors(0), V=lord.backend.get_factors(1), rmse=rmse)
 
     cpu = cpu_blas = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(lord, by_user, by_item, k, args)
         cpu_blas = cpu_baseline_blas(lord, by_user, by_item, k, args)
 
@@ -443,11 +472,14 @@ def main():
                        "lambda": 0.05, "parallelism": (f"row-shard x{world} + direct all-gather ({lord.exchangePath})" if args.item_sharding == "rows" else
                                                        f"users in 8 bands over {world} rank(s): items' Gramians reduce-scattered, item rows all-gathered ({lord.exchangePath})")
                        if world > 1 else "1 GPU", "itemStepSharding": args.item_sharding},
-            "rmse_in_sample_after_iters": rmse, "iters_run": args.steps + args.warmup,
-            "rmse_ms": rmse_ms, "rmse_ratings": val.nnz, "rmse_ratings_per_s": (val.nnz / (rmse_ms * 1e-3)) if rmse_ms else None,
-            "roofline": roofline, "exchange": exchange, "cpu_baseline": cpu, "cpu_baseline_blas": cpu_blas,
+            "iters_run": args.steps + args.warmup, "roofline": roofline, "exchange": exchange,
             "setup_s": {"generate": round(t_gen, 2), "prepare": round(t_prep, 2)},
         }
+        if want_rmse:
+            out.update({"rmse_in_sample_after_iters": rmse, "rmse_ms": rmse_ms, "rmse_ratings": val.nnz,
+                        "rmse_ratings_per_s": (val.nnz / (rmse_ms * 1e-3)) if rmse_ms else None})
+        if args.full:
+            out.update({"cpu_baseline": cpu, "cpu_baseline_blas": cpu_blas})
         if step_info is not None:
             out["step_info"] = step_info
         print(json.dumps(out), flush=True)
@@ -457,6 +489,34 @@ def main():
         dist.destroy_process_group()
     if not consistent:
         sys.exit("bench.py: the replicas of the factor matrices differ between the ranks after the last exchange")
+
+
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs: all files together stay below 64 MB (row ids and .npy headers included)
+
+
+def dump_outputs(path, lord):
+    """--dump-outputs DIR: the factor matrices as the last timed step left them (what EmfLord's caller reads back after
+    alsTrainIter()), DIR/U.npy and DIR/V.npy in the run's own precision.  The smaller matrix is placed first and whole when it
+    fits half the budget; a matrix that does not fit what is left is cut to a sample of its rows, drawn without replacement from
+    a fixed seed and kept in ascending order, with the row ids beside it in DIR/<name>_rows.npy (float64: exact below 2^53)."""
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    left = DUMP_BUDGET_BYTES
+    mats = sorted((("U", lord.backend.factors(0)), ("V", lord.backend.factors(1))), key=lambda m: m[1].numel())
+    for n, (name, f) in enumerate(mats):
+        share = left // (len(mats) - n)
+        if f.numel() * f.element_size() <= share:
+            a = f.cpu().numpy()
+            if os.path.exists(os.path.join(path, name + "_rows.npy")):
+                os.remove(os.path.join(path, name + "_rows.npy"))  # (left by a run of a larger workload into the same DIR)
+        else:
+            rows = max(1, share // (f.shape[1] * f.element_size() + 8))
+            idx = np.sort(np.random.default_rng(20260004).choice(f.shape[0], size=rows, replace=False))
+            a = f.index_select(0, torch.from_numpy(idx).to(f.device)).cpu().numpy()
+            np.save(os.path.join(path, name + "_rows.npy"), idx.astype(np.float64))
+            left -= idx.size * 8
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+        left -= a.nbytes
 
 
 def transport_ab(args, dist, ds, k, max_rating, local_rank, dev, barrier, shards):

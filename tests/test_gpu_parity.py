@@ -857,7 +857,7 @@ def test_bench_starts_its_own_ranks(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--same-device", "--backend", "gloo",
-                        "--transport", "ipc", "--workload", "ml1m", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+                        "--transport", "ipc", "--workload", "ml1m", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -1038,4 +1038,34 @@ def test_planes_row_kernel_against_the_float_gather():
     r = subprocess.run([sys.executable, os.path.join(root, "tests", "tools", "x6p_check.py")], capture_output=True, text=True, timeout=900)
     print(r.stdout[-1500:])
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
+
+
+@pytest.mark.gpu
+def test_bench_dumps_the_outputs_of_its_last_step(tmp_path):
+    """`bench.py --dump-outputs DIR`: a plain run (ML-100k shape, 3 timed iterations after 1 warm-up) writes both factor matrices
+    whole (they fit the 64 MB) in the run's precision, prints a line whose steps and ms_per_step are those of the timed loop and
+    that carries none of the --full passes; a second run with the same arguments starts from the same inputs and must write the
+    same bytes (each row is solved by its own wave or workgroup in a fixed order of sums)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    outs = []
+    for name in ("a", "b"):
+        d = tmp_path / name
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--workload", "ml100k", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        line = json.loads(lines[0])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["iters_run"] == 4 and line["dtype"] == "f32"
+        assert line["ms_per_step"] > 0 and abs(line["value"] - line["config"]["nnz"] / (line["ms_per_step"] * 1e-3)) <= 1e-9 * line["value"]
+        assert not [key for key in line if key.startswith("rmse") or key.startswith("cpu_baseline")]
+        assert sorted(p.name for p in d.iterdir()) == ["U.npy", "V.npy"]
+        U, V = np.load(d / "U.npy"), np.load(d / "V.npy")
+        assert U.dtype == np.float32 and V.dtype == np.float32 and U.shape == (943, 20) and V.shape == (1682, 20)
+        assert np.isfinite(U).all() and np.isfinite(V).all() and np.abs(U).max() > 0 and np.abs(V).max() > 0
+        outs.append((U, V))
+    assert np.array_equal(outs[0][0], outs[1][0]) and np.array_equal(outs[0][1], outs[1][1])
 
