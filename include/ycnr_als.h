@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define YCNR_ALS_ABI_VERSION 4 /* 4: + ycnr_als_comm_info, ycnr_als_last_rmse_ms (nothing changed or removed) */
+#define YCNR_ALS_ABI_VERSION 4 /* 4: + ycnr_als_comm_info, ycnr_als_last_rmse_ms (nothing changed or removed); later, still 4: + ycnr_als_recommend */
 
 /* error codes */
 #define YCNR_OK 0
@@ -419,6 +419,31 @@ int ycnr_csr_transpose(int dtype, int64_t rows, int64_t cols, const int64_t *row
 int ycnr_recommend_items(int dtype, int32_t k, int64_t nUsers, const void *userRows, int64_t totalItems, const void *itemFactors,
                          const int64_t *skipPtr, const int32_t *skipIds, double globalAvgShift, double minRecommendRating,
                          int32_t limit, int32_t *outIds, double *outPredict, int32_t *outCount, double *deviceMs);
+
+/* The resident form: top-N for users of a handle that holds (has just trained) both matrices -- what the reference does after
+ * train() with the factors it kept (_saveCalcResultsToRecommender), one recommendItemsForUser per request
+ * (lib/YcnrController.js:227-284, predict = EmfBase._alsPredict, EmfBase.js:825-827).  Semantics and output layout are
+ * those of ycnr_recommend_items; the matrices are the handle's own on the device:
+ *   userIds    nUsers 0-based row ids of the user matrix, any order, repeats allowed (host array)
+ *   skipPtr    nUsers + 1 offsets relative to the request (skipPtr[0] == 0); skipIds strictly ascending per user, ids
+ *              outside the catalogue match nothing
+ *   limit      1..4096; at most limit - 1 items per user, best first, equal predicts by lower item id; an item competes
+ *              only if predict >= minRecommendRating (NaN never does); unused slots -1 / 0
+ * Every predict has the bits ycnr_recommend_items computes from the same rows.  For limit <= 64 (and factorsCount small
+ * enough for 16 padded user rows in 48 KB of LDS) scores and selection are one kernel and no score matrix exists; beyond,
+ * the three kernels of ycnr_recommend_items run on the handle's matrices, in batches whose scores stay below 1 GB.
+ * YCNR_ERR_INVALID (outputs untouched): null pointers, limit outside 1..4096, an id outside [0, totalUsersCount), bad
+ * skip lists.  The call is enqueued on the handle's stream, so it runs behind every half-step in flight (like
+ * ycnr_als_rmse) and returns with the results on the host; its device buffers stay with the handle (a second call of
+ * the same size allocates nothing).  With a communicator it is LOCAL and NOT collective: it reads this rank's copies of
+ * both matrices, whatever they hold (call ycnr_als_sync first where a half-step's exchange may still be landing).
+ * deviceMs (may be NULL): the kernels, between two HIP events on the handle's stream.
+ * The environment variable YCNR_RECOMMEND_VALU (the A/B switch of ycnr_recommend_items: scores by its 16-lane-group kernel
+ * instead of the matrix cores) applies here too, so that the two entries keep computing the same bits: with it set there is no
+ * fused path, every call goes through the score matrix. */
+int ycnr_als_recommend(ycnr_als *h, int64_t nUsers, const int32_t *userIds, const int64_t *skipPtr, const int32_t *skipIds,
+                       double globalAvgShift, double minRecommendRating, int32_t limit, int32_t *outIds, double *outPredict,
+                       int32_t *outCount, double *deviceMs);
 
 #ifdef __cplusplus
 }

@@ -615,6 +615,36 @@ napi_value RecommendItems(napi_env env, napi_callback_info info) {
   return num(env, ms);
 }
 
+// recommend(handle, userIds: Int32Array, skipPtr, skipIds: Int32Array, globalAvgShift, minRecommendRating, limit,
+//           outIds: Int32Array(nUsers * limit), outPredict: Float64Array(nUsers * limit), outCount: Int32Array(nUsers)) -> kernel ms
+// (ycnr_als_recommend: top-N from the handle's own factor matrices)
+napi_value Recommend(napi_env env, napi_callback_info info) {
+  size_t argc = 10;
+  napi_value a[10];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, a, nullptr, nullptr));
+  Handle *hd = argc >= 10 ? handle_of(env, a[0]) : nullptr;
+  if (!hd) return throw_msg(env, "recommend(handle, userIds, skipPtr, skipIds, shift, minRating, limit, outIds, outPredict, outCount)");
+  View ui = view_of(env, a[1]), sp = view_of(env, a[2]), sk = view_of(env, a[3]), oi = view_of(env, a[7]), op = view_of(env, a[8]),
+       oc = view_of(env, a[9]);
+  int64_t limit;
+  double shift, minRating;
+  std::vector<int64_t> skipPtr;
+  if (!ui.ok || !sp.ok || !sk.ok || !oi.ok || !op.ok || !oc.ok || !get_double(env, a[4], &shift) || !get_double(env, a[5], &minRating) ||
+      !get_int(env, a[6], &limit) || !to_i64(sp, skipPtr) || ui.type != napi_int32_array || sk.type != napi_int32_array ||
+      oi.type != napi_int32_array || op.type != napi_float64_array || oc.type != napi_int32_array)
+    return throw_msg(env, "invalid type!");  // cpp_utils/cpp_utils.js:12
+  const size_t nUsers = ui.length;
+  if (limit < 1 || skipPtr.size() != nUsers + 1 || skipPtr.back() < 0 || (size_t)skipPtr.back() > sk.length || oi.length < nUsers * (size_t)limit ||
+      op.length < nUsers * (size_t)limit || oc.length < nUsers)
+    return throw_msg(env, "array lengths do not match");
+  double ms = 0;
+  int rc = ycnr_als_recommend(hd->h, (int64_t)nUsers, static_cast<const int32_t *>(ui.data), skipPtr.data(), static_cast<const int32_t *>(sk.data), shift,
+                              minRating, (int32_t)limit, static_cast<int32_t *>(oi.data), static_cast<double *>(op.data),
+                              static_cast<int32_t *>(oc.data), &ms);
+  if (rc) return throw_last(env, "recommend", rc);
+  return num(env, ms);
+}
+
 // N2: csrFromTriplets(rowIdx: Int32Array, colIdx: Int32Array, vals, rows, cols, rowPtr: Float64Array(rows+1) out,
 //                     indx: Int32Array(n) out, outVals out) -> kernel ms
 napi_value CsrFromTriplets(napi_env env, napi_callback_info info) {
@@ -737,6 +767,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"getFactors", nullptr, GetFactors, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"step", nullptr, Step, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"rmse", nullptr, Rmse, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+      {"recommend", nullptr, Recommend, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"splitToSets", nullptr, SplitToSets, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"ratingStats", nullptr, RatingStats, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"csrFromTriplets", nullptr, CsrFromTriplets, nullptr, nullptr, nullptr, napi_enumerable, nullptr},

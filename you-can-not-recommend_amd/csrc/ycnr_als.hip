@@ -15,8 +15,10 @@
 #include "prep_kernels.hip.h"
 #include <hipcub/hipcub.hpp>
 #include "prep_kernels.hip.h"
+#include "recommend_kernels.hip.h"
 
 #include <algorithm>
+#include <cfloat>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -1038,6 +1040,14 @@ struct ycnr_als {
   bool exchangedInStep = false;
   Ratings rmse[2];
   double lastRmseMs = -1.0;  // device time of the last ycnr_als_rmse (its kernel, HIP events on the handle's stream)
+  // ycnr_als_recommend: its device buffers grow on demand and stay (a second call of the same size allocates nothing)
+  struct RecBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+  };
+  enum { REC_USER_IDS, REC_SKIP_PTR, REC_SKIP, REC_PART_V, REC_PART_I, REC_IDS, REC_PRED, REC_CNT, REC_ROWS, REC_SCORES, REC_NBUF };
+  RecBuf rec[REC_NBUF];
+  hipEvent_t recEv[2] = {nullptr, nullptr};
   ErrInfo *dErr = nullptr;
   // The error record is never reset on the device: its count only grows, the host remembers what it has seen
   // (errSeen) and gets the record through an 8-byte copy into page-locked memory at the end of every half-step
@@ -1561,6 +1571,10 @@ int ycnr_als_destroy(ycnr_als *h) {
     if (h->padded[s]) (void)hipFree(h->padded[s]);
     if (h->planes[s]) (void)hipFree(h->planes[s]);
   }
+  for (ycnr_als::RecBuf &b : h->rec)
+    if (b.p) (void)hipFree(b.p);
+  for (hipEvent_t ev : h->recEv)
+    if (ev) (void)hipEventDestroy(ev);
   if (h->dErr) (void)hipFree(h->dErr);
   if (h->hErr) (void)hipHostFree(h->hErr);
   if (h->dZeros) (void)hipFree(h->dZeros);
@@ -2867,6 +2881,164 @@ int ycnr_als_last_rmse_ms(ycnr_als *h, double *ms) {
   if (!h || !ms) return fail(YCNR_ERR_INVALID, "null argument");
   if (h->lastRmseMs < 0) return fail(YCNR_ERR_STATE, "last_rmse_ms: no RMSE pass has run on this handle");
   *ms = h->lastRmseMs;
+  return YCNR_OK;
+}
+
+// ---- top-N recommend from the handle's own matrices (recommend_kernels.hip.h) ----
+extern "C++" {
+namespace {
+int rec_reserve(ycnr_als::RecBuf &b, size_t bytes) {
+  if (bytes <= b.cap) return YCNR_OK;
+  if (b.p) (void)hipFree(b.p);
+  b.p = nullptr;
+  b.cap = 0;
+  HIP_TRY(hipMalloc(&b.p, bytes));
+  b.cap = bytes;
+  return YCNR_OK;
+}
+constexpr int64_t kRecFusedBatch = 65536;  // users per launch of the fused kernel (bounds the partial lists)
+
+// one batch of the fused path: scores + per-workgroup lists, then the merge into the output layout
+template <typename T>
+void launch_topn(ycnr_als *h, int64_t u0, int64_t nb, unsigned yblk, size_t lds, double shift, double thr, int take, int limit) {
+  const unsigned ublk = (unsigned)((nb + 15) / 16);
+  hipLaunchKernelGGL(recommend_topn_kernel<T>, dim3(ublk, yblk), dim3(256), lds, h->stream, (const T *)h->factors[YCNR_BY_USER],
+                     (const int32_t *)h->rec[ycnr_als::REC_USER_IDS].p + u0, nb, (const T *)h->factors[YCNR_BY_ITEM], h->opt.totalItemsCount,
+                     (int)h->opt.factorsCount, shift, thr, (const int64_t *)h->rec[ycnr_als::REC_SKIP_PTR].p + u0,
+                     (const int32_t *)h->rec[ycnr_als::REC_SKIP].p, take, (double *)h->rec[ycnr_als::REC_PART_V].p,
+                     (int32_t *)h->rec[ycnr_als::REC_PART_I].p);
+  hipLaunchKernelGGL(recommend_topn_merge_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, h->stream, (const double *)h->rec[ycnr_als::REC_PART_V].p,
+                     (const int32_t *)h->rec[ycnr_als::REC_PART_I].p, nb, (int)yblk, take, limit, (int32_t *)h->rec[ycnr_als::REC_IDS].p + u0 * limit,
+                     (double *)h->rec[ycnr_als::REC_PRED].p + u0 * limit, (int32_t *)h->rec[ycnr_als::REC_CNT].p + u0);
+}
+
+// one batch of the score-matrix path: the kernels of ycnr_recommend_items on the gathered user rows
+template <typename T>
+void launch_scores_select(ycnr_als *h, int64_t u0, int64_t nb, bool valu, bool anySkip, double shift, double minRating, int take, int limit) {
+  const int k = h->opt.factorsCount;
+  const int64_t totalItems = h->opt.totalItemsCount;
+  const size_t kp = (size_t)((k + 15) & ~15);
+  T *rows = (T *)h->rec[ycnr_als::REC_ROWS].p;
+  double *scores = (double *)h->rec[ycnr_als::REC_SCORES].p;
+  const int64_t *skipPtr = (const int64_t *)h->rec[ycnr_als::REC_SKIP_PTR].p + u0;
+  hipLaunchKernelGGL(gather_rows_kernel<T>, dim3((unsigned)((nb * k + 255) / 256)), dim3(256), 0, h->stream, (const T *)h->factors[YCNR_BY_USER],
+                     (const int32_t *)h->rec[ycnr_als::REC_USER_IDS].p + u0, nb, k, rows);
+  const unsigned ublk = (unsigned)((nb + 15) / 16);
+  const unsigned yblk = (unsigned)std::max<int64_t>(1, std::min<int64_t>((totalItems + 63) / 64, (8 * device_cus() + ublk - 1) / ublk));
+  if (valu)
+    hipLaunchKernelGGL((recommend_scores_kernel<T, 1>), dim3((unsigned)nb), dim3(256), (size_t)k * sizeof(T), h->stream, (const T *)rows, nb,
+                       (const T *)h->factors[YCNR_BY_ITEM], totalItems, k, shift, minRating, scores);
+  else
+    hipLaunchKernelGGL(recommend_scores_mfma_kernel<T>, dim3(ublk, yblk), dim3(256), 16 * kp * sizeof(T), h->stream, (const T *)rows, nb,
+                       (const T *)h->factors[YCNR_BY_ITEM], totalItems, k, shift, minRating, scores);
+  if (anySkip)
+    hipLaunchKernelGGL(recommend_skip_kernel, dim3((unsigned)nb), dim3(256), 0, h->stream, skipPtr, (const int32_t *)h->rec[ycnr_als::REC_SKIP].p, totalItems,
+                       scores);
+  hipLaunchKernelGGL(recommend_select_kernel, dim3((unsigned)nb), dim3(256), 0, h->stream, scores, totalItems, take, limit,
+                     (int32_t *)h->rec[ycnr_als::REC_IDS].p + u0 * limit, (double *)h->rec[ycnr_als::REC_PRED].p + u0 * limit,
+                     (int32_t *)h->rec[ycnr_als::REC_CNT].p + u0);
+}
+}  // namespace
+}  // extern "C++"
+
+int ycnr_als_recommend(ycnr_als *h, int64_t nUsers, const int32_t *userIds, const int64_t *skipPtr, const int32_t *skipIds,
+                       double globalAvgShift, double minRecommendRating, int32_t limit, int32_t *outIds, double *outPredict,
+                       int32_t *outCount, double *deviceMs) {
+  if (!h) return fail(YCNR_ERR_INVALID, "null handle");
+  if (nUsers < 0 || limit < 1 || limit > 4096) return fail(YCNR_ERR_INVALID, "ycnr_als_recommend: bad nUsers / limit");
+  if (nUsers == 0) {
+    if (deviceMs) *deviceMs = 0.0;
+    return YCNR_OK;
+  }
+  if (!userIds || !skipPtr || !outIds || !outPredict || !outCount) return fail(YCNR_ERR_INVALID, "ycnr_als_recommend: null argument");
+  if (skipPtr[0] != 0) return fail(YCNR_ERR_INVALID, "ycnr_als_recommend: skipPtr[0] != 0");
+  for (int64_t u = 0; u < nUsers; ++u) {
+    if (userIds[u] < 0 || userIds[u] >= h->opt.totalUsersCount)
+      return fail(YCNR_ERR_INVALID, "ycnr_als_recommend: user id %d at position %lld is outside [0, %lld)", userIds[u], (long long)u,
+                  (long long)h->opt.totalUsersCount);
+    if (skipPtr[u + 1] > skipPtr[u] && !skipIds) return fail(YCNR_ERR_INVALID, "ycnr_als_recommend: null skipIds");
+    if (skipPtr[u + 1] < skipPtr[u]) return fail(YCNR_ERR_INVALID, "ycnr_als_recommend: skipPtr decreases at user %lld", (long long)u);
+    for (int64_t q = skipPtr[u] + 1; q < skipPtr[u + 1]; ++q)
+      if (skipIds[q] <= skipIds[q - 1])
+        return fail(YCNR_ERR_INVALID, "ycnr_als_recommend: skip ids of user %lld are not strictly ascending", (long long)u);
+  }
+  const int64_t nSkip = skipPtr[nUsers];
+  const int k = h->opt.factorsCount;
+  const int64_t totalItems = h->opt.totalItemsCount;
+  const size_t ts = h->ts();
+  const int take = limit - 1;  // lib/YcnrController.js:268-269
+  HIP_TRY(hipSetDevice(h->opt.device));
+  if (take == 0) {  // the reference returns nothing; still ordered behind the half-steps in flight
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    for (int64_t u = 0; u < nUsers; ++u) {
+      outIds[u] = -1;
+      outPredict[u] = 0.0;
+      outCount[u] = 0;
+    }
+    if (deviceMs) *deviceMs = 0.0;
+    return YCNR_OK;
+  }
+  // the same choice of score kernel as ycnr_recommend_items, so that the predicts are the same bits -- its A/B switch
+  // YCNR_RECOMMEND_VALU included: with the variable set there is NO fused path here (include/ycnr_als.h says so; a timing taken
+  // with it set is the score-matrix path's)
+  const size_t kp = (size_t)((k + 15) & ~15);
+  const bool valu = getenv("YCNR_RECOMMEND_VALU") != nullptr || 16 * kp * ts > 48 * 1024;
+  const bool fused = !valu && take <= kTopMaxTake;
+  typedef ycnr_als A;
+  if (int rc = rec_reserve(h->rec[A::REC_USER_IDS], (size_t)nUsers * 4)) return rc;
+  if (int rc = rec_reserve(h->rec[A::REC_SKIP_PTR], (size_t)(nUsers + 1) * 8)) return rc;
+  if (int rc = rec_reserve(h->rec[A::REC_SKIP], std::max<size_t>((size_t)nSkip * 4, 8))) return rc;
+  if (int rc = rec_reserve(h->rec[A::REC_IDS], (size_t)nUsers * limit * 4)) return rc;
+  if (int rc = rec_reserve(h->rec[A::REC_PRED], (size_t)nUsers * limit * 8)) return rc;
+  if (int rc = rec_reserve(h->rec[A::REC_CNT], (size_t)nUsers * 4)) return rc;
+  // the item range of a user tile over enough workgroups to fill the chip four times, at least 16 tiles (4 per wave) each
+  const int64_t ntiles = (totalItems + 15) / 16;
+  auto parts_of = [&](int64_t nb) {
+    const int64_t ublk = (nb + 15) / 16;
+    return std::max<int64_t>(1, std::min<int64_t>((ntiles + 15) / 16, (4 * (int64_t)device_cus() + ublk - 1) / ublk));
+  };
+  const int64_t batch = fused ? std::min(nUsers, kRecFusedBatch)
+                              : std::max<int64_t>(1, std::min<int64_t>(nUsers, ((int64_t)1 << 27) / std::max<int64_t>(1, totalItems)));  // scores <= 1 GB
+  if (fused) {
+    const int64_t last = nUsers % batch ? nUsers % batch : batch;
+    const size_t lists = (size_t)std::max(batch * parts_of(batch), last * parts_of(last));
+    if (int rc = rec_reserve(h->rec[A::REC_PART_V], lists * take * 8)) return rc;
+    if (int rc = rec_reserve(h->rec[A::REC_PART_I], lists * take * 4)) return rc;
+  } else {
+    if (int rc = rec_reserve(h->rec[A::REC_ROWS], (size_t)batch * k * ts)) return rc;
+    if (int rc = rec_reserve(h->rec[A::REC_SCORES], (size_t)batch * totalItems * 8)) return rc;
+  }
+  for (hipEvent_t &ev : h->recEv)
+    if (!ev) HIP_TRY(hipEventCreate(&ev));
+  // everything below is enqueued on the handle's stream: behind the half-steps in flight, like ycnr_als_rmse
+  HIP_TRY(hipMemcpyAsync(h->rec[A::REC_USER_IDS].p, userIds, (size_t)nUsers * 4, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(h->rec[A::REC_SKIP_PTR].p, skipPtr, (size_t)(nUsers + 1) * 8, hipMemcpyHostToDevice, h->stream));
+  if (nSkip) HIP_TRY(hipMemcpyAsync(h->rec[A::REC_SKIP].p, skipIds, (size_t)nSkip * 4, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipEventRecord(h->recEv[0], h->stream));
+  const double thr = minRecommendRating < -DBL_MAX ? -DBL_MAX : minRecommendRating;  // (-inf is "out" in the score matrix: it never competes)
+  const size_t lds = std::max<size_t>(16 * kp * ts, (size_t)64 * take * 12);
+  for (int64_t u0 = 0; u0 < nUsers; u0 += batch) {
+    const int64_t nb = std::min(batch, nUsers - u0);
+    if (fused) {
+      if (h->opt.dtype == YCNR_F32) launch_topn<float>(h, u0, nb, (unsigned)parts_of(nb), lds, globalAvgShift, thr, take, limit);
+      else launch_topn<double>(h, u0, nb, (unsigned)parts_of(nb), lds, globalAvgShift, thr, take, limit);
+    } else {
+      if (h->opt.dtype == YCNR_F32) launch_scores_select<float>(h, u0, nb, valu, nSkip > 0, globalAvgShift, minRecommendRating, take, limit);
+      else launch_scores_select<double>(h, u0, nb, valu, nSkip > 0, globalAvgShift, minRecommendRating, take, limit);
+    }
+    hipError_t le = hipGetLastError();
+    if (le != hipSuccess) return fail(YCNR_ERR_HIP, "recommend launch: %s", hipGetErrorString(le));
+  }
+  HIP_TRY(hipEventRecord(h->recEv[1], h->stream));
+  HIP_TRY(hipMemcpyAsync(outIds, h->rec[A::REC_IDS].p, (size_t)nUsers * limit * 4, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(outPredict, h->rec[A::REC_PRED].p, (size_t)nUsers * limit * 8, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(outCount, h->rec[A::REC_CNT].p, (size_t)nUsers * 4, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (deviceMs) {
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, h->recEv[0], h->recEv[1]));
+    *deviceMs = ms;
+  }
   return YCNR_OK;
 }
 

@@ -289,6 +289,40 @@ class EmfLord extends EmfMaster {
     });
   }
 
+  /** YcnrController's getter (lib/YcnrController.js:50-55): the configured value of the dbType, else 0.7 maxRating */
+  get minRecommendRating() {
+    const o = this.options, v = o.minRecommendRating && o.minRecommendRating[o.dbType];
+    return v ? v : o.maxRating[o.dbType] * 0.7;
+  }
+
+  /**
+   * YcnrController.recommendItemsForUser (lib/YcnrController.js:227-284) for a batch of 0-based user ids, from the
+   * factors the trainer handle holds (no download): per user [{predict, id: itemId + 1}], best first, at most
+   * limit - 1 entries (:261-271).  Left out: every rating of the user in the data set this Lord was prepared with --
+   * train, validate and test, as the reference's SQL over malrec_ratings (:233-240) -- and the optional
+   * unratedItems[i] (0-based ids, :243-248).  The shift is this Lord's globalAvgShift.
+   * With several GPU processes (replicated layout) the call is local to this one.  It needs no sync of its own: native.step
+   * is ycnr_als_step (enqueue + ycnr_als_sync, exchange included), so no half-step is in flight when this runs.
+   */
+  recommendItemsForUsers(userIds, limit, minRecommendRating, unratedItems) {
+    if (this.handle === null) throw new Error('recommendItemsForUsers: prepareToTrain has not been called');
+    if (this.bands && this.options.world > 1)
+      throw new Error("recommendItemsForUsers: with itemStepSharding 'bands' the user matrix is not replicated on every rank; " +
+        'recommend from a Lord that holds both matrices');
+    const ds = this.dataset, sets = [ds.trainByUser, ds.validate, ds.test].filter((c) => c);
+    const ids = Array.from(userIds);
+    if (unratedItems && unratedItems.length != ids.length) throw new Error('recommendItemsForUsers: unratedItems needs one entry (or null) per user');
+    const skipLists = ids.map((u, i) => {
+      if (!(u >= 0 && u < this.totalUsersCount)) throw new Error('recommendItemsForUsers: user id outside [0, ' + this.totalUsersCount + ')');
+      const seen = new Set();
+      for (const c of sets) for (let p = c.rowPtr[u]; p < c.rowPtr[u + 1]; p++) seen.add(c.indx[p]);
+      if (unratedItems && unratedItems[i]) for (const id0 of unratedItems[i]) seen.add(Number(id0));
+      return Int32Array.from(seen).sort();
+    });
+    const thr = (minRecommendRating === undefined || minRecommendRating === null) ? this.minRecommendRating : minRecommendRating;
+    return als.recommend(this.handle, ids, skipLists, this.globalAvgShift || 0, thr, limit || 20);
+  }
+
   /** @param string stepType 'rmseValidate', 'rmseTest' (EmfLord.js:1043-1081) */
   calcRmse(stepType, useGlobalAvgShift) {
     if (useGlobalAvgShift && this.options.alg != 'als')

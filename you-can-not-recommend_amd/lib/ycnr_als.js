@@ -137,5 +137,27 @@
     return recItems;
   };
 
+  /**
+   * The same for a batch of users of a trainer handle, from the factor matrices the handle holds on the device
+   * (ycnr_als_recommend): userIds 0-based rows of the user matrix, skipLists[i] the SORTED UNIQUE 0-based item ids to
+   * leave out for userIds[i]. Runs behind the half-steps in flight. Returns per user [{predict, id}] (id 1-based).
+   */
+  als.recommend = function (handle, userIds, skipLists, globalAvgShift, minRecommendRating, limit) {
+    limit = limit || 20;
+    var n = userIds.length, skipPtr = new Float64Array(n + 1), i, j;
+    for (i = 0; i < n; i++) skipPtr[i + 1] = skipPtr[i] + skipLists[i].length;
+    var skipIds = new Int32Array(skipPtr[n]);
+    for (i = 0; i < n; i++) skipIds.set(skipLists[i], skipPtr[i]);
+    var ids = new Int32Array(n * limit), pred = new Float64Array(n * limit), cnt = new Int32Array(n);
+    native.recommend(handle, Int32Array.from(userIds), skipPtr, skipIds, globalAvgShift || 0, minRecommendRating, limit, ids, pred, cnt);
+    var out = [];
+    for (i = 0; i < n; i++) {
+      var recItems = [];
+      for (j = 0; j < cnt[i]; j++) recItems.push({ predict: pred[i * limit + j], id: ids[i * limit + j] + 1 });
+      out.push(recItems);
+    }
+    return out;
+  };
+
   module.exports = als;
 }());

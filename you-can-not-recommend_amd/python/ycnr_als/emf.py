@@ -334,6 +334,11 @@ class HipBackend:
         self.torch.cuda.current_stream(self.device).synchronize()  # (as step())
         return self.dev.rmse(which, shift, portion_row_end)
 
+    def recommend(self, user_ids, skip_ptr, skip_ids, shift, min_rating, limit):
+        """top-N from the resident factors (ycnr_als_recommend): (ids, predicts, counts), ids 0-based with -1 padding"""
+        self.torch.cuda.current_stream(self.device).synchronize()  # (as step())
+        return self.dev.recommend(user_ids, skip_ptr, skip_ids, shift, min_rating, limit)[:3]
+
     def destroy(self):
         self.dev.destroy()
 
@@ -759,6 +764,54 @@ class EmfLord:
         return self.rmse
 
     # -- results (EmfManager.js:158-176,463-570) ---------------------------------------------
+    # -- recommend (YcnrController.recommendItemsForUser, lib/YcnrController.js:227-284) --
+    @property
+    def minRecommendRating(self):
+        """YcnrController's getter (lib/YcnrController.js:50-55): the configured value of the dbType, else 0.7 maxRating."""
+        v = (self.options.get("minRecommendRating") or {}).get(self.options["dbType"])
+        return v if v else self.options["maxRating"][self.options["dbType"]] * 0.7
+
+    def recommendSkipLists(self, userIds, unratedItems=None):
+        """Per requested user the sorted unique 0-based item ids that must not be offered: every rating of the user in the
+        dataset this Lord was prepared with -- train, validate and test, as the reference's SQL over malrec_ratings
+        (YcnrController.js:233-240) -- plus the optional unratedItems[i] (0-based ids, :243-248).  Returns (skipPtr, skipIds)."""
+        ds = self.dataset
+        if getattr(self, "_recSets", (None, None))[0] is not ds:  # (host copies of a device-resident dataset: once)
+            self._recSets = (ds, [c.numpy() for c in (ds.train_by_user, ds.validate, ds.test) if c is not None])
+        sets = self._recSets[1]
+        lists = []
+        for i, u in enumerate(userIds):
+            parts = [np.asarray(c.indx[c.rowPtr[u]:c.rowPtr[u + 1]], np.int64) for c in sets]
+            if unratedItems is not None and unratedItems[i] is not None:
+                parts.append(np.asarray(unratedItems[i], np.int64).reshape(-1))
+            lists.append(np.unique(np.concatenate(parts)).astype(np.int32) if parts else np.zeros(0, np.int32))
+        ptr = np.zeros(len(lists) + 1, np.int64)
+        ptr[1:] = np.cumsum([len(x) for x in lists])
+        return ptr, (np.concatenate(lists) if lists else np.zeros(0, np.int32))
+
+    def recommendItemsForUsers(self, userIds, limit=20, minRecommendRating=None, unratedItems=None):
+        """recommendItemsForUser for a batch of 0-based user ids, from the factors the backend holds (no download): per
+        user the list of {id: itemId + 1, predict}, best first, at most limit - 1 entries (YcnrController.js:261-271).
+        The items a user has rated (and unratedItems[i], 0-based) are left out; the shift is this Lord's globalAvgShift.
+        With several ranks (replicated layout) the call is local to this rank.  It needs no ycnr_als_sync of its own: this
+        host's half-steps are synchronous (backend.step = enqueue + sync, exchange included), so none is in flight here."""
+        if self.backend is None:
+            raise RuntimeError("recommendItemsForUsers: prepareToTrain has not been called")
+        if self.bands is not None and self.world > 1:
+            raise RuntimeError("recommendItemsForUsers: with itemStepSharding='bands' the user matrix is not replicated on "
+                               "every rank; recommend from a Lord that holds both matrices (loadCalcResults on one rank)")
+        if not hasattr(self.backend, "recommend"):
+            raise RuntimeError("recommendItemsForUsers: the backend has no recommend(); nothing is computed on the host")
+        uid = np.asarray(userIds, np.int64).reshape(-1)
+        if len(uid) and (uid.min() < 0 or uid.max() >= self.totalUsersCount):
+            raise ValueError("recommendItemsForUsers: user id outside [0, %d)" % self.totalUsersCount)
+        if unratedItems is not None and len(unratedItems) != len(uid):
+            raise ValueError("recommendItemsForUsers: unratedItems needs one entry (or None) per user")
+        thr = self.minRecommendRating if minRecommendRating is None else minRecommendRating
+        ptr, skip = self.recommendSkipLists(uid, unratedItems)
+        ids, pred, cnt = self.backend.recommend(uid.astype(np.int32), ptr, skip, float(self.globalAvgShift), float(thr), int(limit))
+        return [[{"id": int(ids[i, j]) + 1, "predict": float(pred[i, j])} for j in range(int(cnt[i]))] for i in range(len(uid))]
+
     def getCalcInfo(self):
         o = self.options
         return {

@@ -360,3 +360,23 @@ class AlsDevice:
         check(self._L.ycnr_als_rmse(self._h, RMSE_SETS[which], float(globalAvgShift), len(ends), ends.ctypes.data,
                                     out.ctypes.data))
         return out
+
+    def recommend(self, userIds, skipPtr, skipIds, globalAvgShift=0.0, minRecommendRating=7.0, limit=20):
+        """recommend_items from the handle's own factor matrices (ycnr_als_recommend): userIds are 0-based rows of the
+        user matrix (any order, repeats allowed), skipPtr / skipIds the CSR of item ids to leave out, relative to the
+        request.  Runs behind the half-steps in flight.  Returns (ids [n x limit] with -1 padding, predicts, counts,
+        kernel ms) like recommend_items."""
+        uid = np.ascontiguousarray(userIds, np.int32).reshape(-1)
+        sp = np.ascontiguousarray(skipPtr, np.int64)
+        sk = np.ascontiguousarray(skipIds, np.int32)
+        n = len(uid)
+        if len(sp) != n + 1:
+            raise ValueError("skipPtr needs one entry per requested user plus one")
+        ids = np.full((n, max(int(limit), 0)), -1, np.int32)
+        pred = np.zeros((n, max(int(limit), 0)), np.float64)
+        cnt = np.zeros(n, np.int32)
+        ms = C.c_double(0.0)
+        check(self._L.ycnr_als_recommend(self._h, n, uid.ctypes.data, sp.ctypes.data, sk.ctypes.data if len(sk) else None,
+                                         float(globalAvgShift), float(minRecommendRating), int(limit), ids.ctypes.data,
+                                         pred.ctypes.data, cnt.ctypes.data, C.byref(ms)))
+        return ids, pred, cnt, ms.value
