@@ -940,7 +940,7 @@ def test_four_rows_per_wave_kernel_against_the_one_row_kernel(tmp_path):
 
 @pytest.mark.gpu
 def test_launch_order_of_the_rows_does_not_change_a_bit(tmp_path):
-    """Large launches take their primal rows in a fixed pseudo-random order instead of longest-first (build_part: waves that share
+    """Large launches take their primal rows in a fixed pseudo-random order instead of longest-first (plan_piece: waves that share
     a SIMD then differ in length and phase); YCNR_ROW_ORDER=0 keeps the sorted order.  Every row is solved by its own wave, so
     both orders must give every factor bit for bit (200 K x 20 K shape at k = 100: ~100 K primal rows on the user side).
     The toggle is read once per process: each result is a child process of bench.py."""

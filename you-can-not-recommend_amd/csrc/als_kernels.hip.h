@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include <stdint.h>
+#include "schedule.h"
 
 // Register budget of the fused Gramian + solve kernel: 2 waves per SIMD = at most 256
 // registers per lane (k = 100 needs 206 and does not spill; 3 would spill 220 B per lane).
@@ -61,24 +62,7 @@
 
 namespace ycnr {
 
-// A wave-level work unit: ratings [beg, end) of the local CSR belong to `row`.
-// slab < 0: the unit covers the whole row and solves it; else it writes partial
-// sums to slab number `slab`.
-struct Unit {
-  int64_t beg;
-  int64_t end;
-  int32_t row;
-  int32_t slab;
-};
-
-// A row whose Gramian was split over nslabs units (slab0 .. slab0+nslabs-1).
-struct SplitRow {
-  int64_t n;  // ratings of the row (for lambda * n)
-  int32_t row;
-  int32_t slab0;
-  int32_t nslabs;
-  int32_t pad;
-};
+// Unit, SplitRow, SlabSum, kFewSlabs: schedule.h (the host-only code that fills them in)
 
 struct ErrInfo {
   int32_t count;     // rows with a non-positive pivot
@@ -3058,7 +3042,6 @@ __global__ __launch_bounds__(64) void als_dual_quad_kernel(StepArgs<float> a, in
 // waves per SIMD).  FEW: no row of the upload has more than kFewSlabs slabs -- the small shapes, where the kernel is a
 // wave of solves: bounded to 168 registers (no scratch where listed) three waves share a SIMD; ML-1M shape user half-step
 // 0.193 -> 0.182 ms.
-constexpr int kFewSlabs = 8;
 template <typename T, int NB, bool LDS_SOLVER, bool E4, bool FEW>
 constexpr int reduce_waves() {
   if (!FEW || sizeof(T) != 4 || LDS_SOLVER) return 1;
@@ -3103,12 +3086,8 @@ __global__ __launch_bounds__(64, (reduce_waves<T, NB, LDS_SOLVER, E4, FEW>())) v
 // als_slab_sum_kernel where a (row, band) segment was cut into several chunks --, the slabs travel to the row's owner, and the
 // owner adds a row's band slabs in band order and solves: the same arithmetic whatever the number of ranks.
 
-// dst slab <- sum of n consecutive source slabs, in order (element offsets into one arena); in double beyond kFewSlabs, as the
-// reduce kernels sum the slabs of a row
-struct SlabSum {
-  int64_t dst, src0;
-  int32_t n, pad;
-};
+// SlabSum (schedule.h): dst slab <- sum of n consecutive source slabs, in order; in double beyond kFewSlabs, as the reduce
+// kernels sum the slabs of a row
 template <typename T>
 __global__ __launch_bounds__(256) void als_slab_sum_kernel(T *arena, const SlabSum *list, int64_t elems) {
   const SlabSum e = list[blockIdx.x];

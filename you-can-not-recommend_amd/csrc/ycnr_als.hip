@@ -14,7 +14,6 @@
 #include "als_gen_kernels.hip.h"
 #include "prep_kernels.hip.h"
 #include <hipcub/hipcub.hpp>
-#include "prep_kernels.hip.h"
 #include "recommend_kernels.hip.h"
 
 #include <algorithm>
@@ -59,29 +58,15 @@ int fail(int code, const char *fmt, ...) {
 constexpr int kMaxFactors = 128;     // float64, and the one-wave-per-row float32 kernels
 constexpr int kMaxFactorsBig = 256;  // float32 through the workgroup-per-row kernels of als_wg_kernels.hip.h
 constexpr int kMaxFactorsAny = 4096; // beyond kMaxFactorsBig (float64: kMaxFactors): the any-k path of als_gen_kernels.hip.h
-constexpr int kGenChunk = 4096;      // ratings per unit of the any-k path (als_gen_kernels.hip.h): every row goes through slabs there
-constexpr int64_t kGenArenaBytes = (int64_t)2 << 30;  // slab arena of that path: rows are solved in batches that fit it
+constexpr int64_t kGenArenaBytes = (int64_t)2 << 30;  // slab arena of the any-k path: rows are solved in batches that fit it
 constexpr int kPairNB = 16;           // block count whose whole rows go Gramian -> slab -> two-wave solve (als_pair_kernels.hip.h): 240 < k <= 256
 constexpr int64_t kPairBatchRows = 4096;   // rows per batch of that path (a slab is 140 KB: 0.57 GB of arena).  One GPU's eighth of C5, ms per
                                            // iteration at 512 / 1024 / 2048 / 3072 / 4096 / 6144 / 8192 / 12288 / 24576 / 98304 rows: 141.6 / 138.0 / 136.7 /
                                            // 136.3 / 136.2 / 136.5 / 137.3 / 139.7 / 138.6 / 137.6 -- short batches leave more of a batch's slabs in the
                                            // last-level cache for its solve, shorter ones pay two kernel tails per batch (YCNR_PAIR_BATCH_ROWS overrides)
-constexpr int kWgChunk = 8192;       // ratings per chunk of a row that is split over workgroups (k > 128)
-#ifndef YCNR_WG_FUSED_MAX
-#define YCNR_WG_FUSED_MAX 8192
-#endif
-constexpr int kWgFusedMax = YCNR_WG_FUSED_MAX;  // longest row one workgroup takes whole (k > 128).  16384 until round 5: a row's Gramian is ONE float32 chain over
-                                     // its ratings / 32 steps, and the item rows of the full C5 that missed the flat 1e-5 against float64 (2 of 54 sampled,
-                                     // 1.09e-5) were whole rows of 8 - 16 K ratings; at 8192: every sampled row within 7.2e-6, item half-step + 1 %
-constexpr int kDefaultChunk = 1024;  // ratings per split unit (and the largest fused row)
-constexpr int kMaxSlabsPerRow = 64;  // heavier rows get proportionally longer chunks
-constexpr int kMaxSlabsPerRowBig = 4096;  // k > 128 (chunks of kWgChunk ratings): an item of the full C5 has 10 M ratings; with 64 slabs its
-                                          // chunks were float32 sums over 156 K ratings each (backward error 0.86 of its gate in round 3);
-                                          // 8192-rating chunks keep every accumulation chain short, the workgroup reduce adds the slabs in order
 constexpr int64_t kBandBytes = (int64_t)96 << 20;  // slice of the fixed matrix one band of chunks gathers from (cache-sized)
 constexpr size_t kErrBytes = 65536;
 constexpr size_t kZeroRowBytes = 32768 + 64;  // >= kMaxFactorsAny doubles: the "row" the dual kernels gather for ratings past a row's end
-constexpr int kMaxDualBlocks = 12;       // dual-form kernels exist for 1..12 blocks of 16 ratings (12: 340 bytes of scratch per lane, still 1.0 ms per C5-shard iteration cheaper than the primal form for rows of 177..192 ratings; 13: 936 bytes and no gain)
 constexpr int kMaxDualBlocksSmallK = 5;  // k <= 128: beyond 80 ratings the row kernel (k x k) is cheaper (MAL scale, k = 100: 6 -> 5 blocks took 0.2 ms off the user half-step once the solve had lost its readlanes and transposes; 4 was slower)
 
 size_t tsize(int dtype) { return dtype == YCNR_F64 ? 8 : 4; }
@@ -104,124 +89,27 @@ struct Ratings {
   }
 };
 
-// a batch of the any-k path: split rows [firstSplit, +nSplit) with their units = slabs [slabBase, +nSlabs)
-struct GenBatch {
-  int32_t firstSplit, nSplit, slabBase, nSlabs;
-};
 
 // the any-k path (als_gen_kernels.hip.h): float32 beyond 256 factors, float64 beyond 128
 bool is_gen(int dtype, int k) { return k > (dtype == YCNR_F32 ? kMaxFactorsBig : kMaxFactors); }
 
-// Batches of consecutive split rows whose slabs fit `arenaSlabs` (at least one row per batch).
-std::vector<GenBatch> gen_batches(const std::vector<SplitRow> &split, int64_t arenaSlabs) {
-  std::vector<GenBatch> out;
-  size_t i = 0;
-  while (i < split.size()) {
-    GenBatch b{(int32_t)i, 0, split[i].slab0, 0};
-    while (i < split.size() && (b.nSplit == 0 || b.nSlabs + split[i].nslabs <= arenaSlabs)) {
-      b.nSlabs += split[i].nslabs;
-      ++b.nSplit;
-      ++i;
-    }
-    out.push_back(b);
-  }
-  return out;
-}
-
-struct Schedule {
+// A piece's plan (schedule.h) on the device: the counters of the plan, and the owner of the lists' device copies and the slabs
+struct Schedule : PlanCounts {
   std::vector<GenBatch> genBatches;
   Unit *dUnits = nullptr;
   SplitRow *dSplit = nullptr;
   void *dSlabs = nullptr;
   float *dRowSlabs = nullptr;  // k > 240: the images of a batch of whole rows between their Gramian and their two-wave solve
   int64_t rowSlabRows = 0;
-  int64_t nUnits = 0, nSplit = 0, nSlabs = 0, solvedRows = 0, fusedRatings = 0;
-  int32_t maxRowSlabs = 0;  // most slabs any split row has
-  // whole-row units: [nSlabs, nSlabs + nPrimal) primal form, then dual classes m = kMaxDualBlocks..1
-  int64_t nPrimal = 0, dualFirst[kMaxDualBlocks + 1] = {}, dualCount[kMaxDualBlocks + 1] = {};
-  int64_t dualRows = 0, dualRatings = 0;
-  double dualFlops = 0;  // flops the dual form executes for those rows: G = Y Y^T (symmetric), Cholesky, x = Y^T w
+  int64_t nUnits = 0, nSplit = 0;
   void release() {
     if (dUnits) (void)hipFree(dUnits);
     if (dSplit) (void)hipFree(dSplit);
     if (dSlabs) (void)hipFree(dSlabs);
     if (dRowSlabs) (void)hipFree(dRowSlabs);
-    dRowSlabs = nullptr;
-    rowSlabRows = 0;
-    dUnits = nullptr;
-    dSplit = nullptr;
-    dSlabs = nullptr;
-    nUnits = nSplit = nSlabs = solvedRows = fusedRatings = nPrimal = dualRows = dualRatings = 0;
-    maxRowSlabs = 0;
-    dualFlops = 0;
-    genBatches.clear();
-    for (int m = 0; m <= kMaxDualBlocks; ++m) dualFirst[m] = dualCount[m] = 0;
+    *this = Schedule();
   }
 };
-
-// Ratings per split unit when the caller leaves it to the library: every chunk costs a 30 KB
-// slab written and read again (k = 100), so chunks should be long -- but a launch wants >= 16
-// units per resident wave (2048 on a 256-CU part at two waves per SIMD) to keep its tail short.
-// MAL item side: 121.5 M ratings on one GPU -> 3072; an eighth of it on each of 8 GPUs -> 1024.
-// Small uploads (below 2 M ratings: the ML-1M shape) are bound by their longest wave, not by slab traffic:
-// there the chunk shrinks, down to 256, so that one round of waves covers the half-step (ML-1M shape, k = 100:
-// 0.62 -> 0.54 ms per iteration with 512; 200 K x 20 K with 20 M ratings is fastest at 1024).
-// nnz: ratings of the whole side; splitNnz: those of its rows above kDefaultChunk ratings (the rows that are split at all).
-// Both describe the side, not the shard: the cuts of a split row must not depend on how the rows are dealt to GPUs.
-int auto_chunk(int64_t nnz, int64_t splitNnz) {
-  if (nnz < (int64_t)2048 * kDefaultChunk)
-    return (int)((std::min<int64_t>(kDefaultChunk, std::max<int64_t>(256, nnz / 2048)) + 3) & ~(int64_t)3);
-  const int64_t c = splitNnz / (2048 * 16);
-  return (int)((std::min<int64_t>(3072, std::max<int64_t>(kDefaultChunk, c)) + 3) & ~(int64_t)3);
-}
-
-// Split rows into wave-level units (the counterpart of EmfLord.splitToPortions,
-// lib/emf/EmfLord.js:510-612, at wave instead of worker-process granularity).
-// rowPtr: local (length nRows + 1, any base).  Units index ratings relative to rowPtr[0].
-void build_schedule(const int64_t *rowPtr, int64_t rowBegin, int64_t nRows, int chunk,
-                    std::vector<Unit> &units, std::vector<SplitRow> &split, int64_t &nSlabs,
-                    int64_t &solvedRows, int64_t splitAbove = -1, int fusedMax = 0, int maxSlabs = kMaxSlabsPerRow) {
-  // fusedMax: longest row that stays one unit (default: chunk)
-  if (fusedMax <= 0) fusedMax = chunk;
-  // splitAbove >= 0 (big path): every row longer than splitAbove goes through slabs, in row
-  // order (no longest-first sort, so that batches are contiguous)
-  // on return units = [split chunks (nSlabs of them) | whole rows]
-  const int64_t base = rowPtr[0];
-  units.clear();
-  split.clear();
-  nSlabs = 0;
-  solvedRows = 0;
-  std::vector<Unit> fused;
-  fused.reserve((size_t)nRows);
-  for (int64_t r = 0; r < nRows; ++r) {
-    const int64_t b = rowPtr[r] - base, e = rowPtr[r + 1] - base, n = e - b;
-    if (n <= 0) continue;  // rows without ratings are never written
-    ++solvedRows;
-    const int32_t row = (int32_t)(rowBegin + r);
-    if (splitAbove >= 0 ? n <= splitAbove : n <= fusedMax) {
-      fused.push_back(Unit{b, e, row, -1});
-      continue;
-    }
-    int64_t ch = chunk;
-    if ((n + ch - 1) / ch > maxSlabs) ch = (n + maxSlabs - 1) / maxSlabs;
-    ch = (ch + 3) & ~(int64_t)3;
-    const int64_t parts = (n + ch - 1) / ch;
-    split.push_back(SplitRow{n, row, (int32_t)nSlabs, (int32_t)parts, 0});
-    for (int64_t p = 0; p < parts; ++p) {
-      const int64_t ub = b + p * ch, ue = std::min(e, ub + ch);
-      units.push_back(Unit{ub, ue, row, (int32_t)(nSlabs + p)});
-    }
-    nSlabs += parts;
-  }
-  // longest first: split chunks (all ~chunk long, longest chunks first), then fused rows by
-  // descending length, so the tail of the launch is made of the cheapest units
-  if (splitAbove < 0)
-    std::stable_sort(units.begin(), units.end(),
-                     [](const Unit &a, const Unit &b) { return (a.end - a.beg) > (b.end - b.beg); });
-  std::stable_sort(fused.begin(), fused.end(),
-                   [](const Unit &a, const Unit &b) { return (a.end - a.beg) > (b.end - b.beg); });
-  units.insert(units.end(), fused.begin(), fused.end());
-}
 
 // environment toggles for A/B experiments from unmodified hosts, read once per process
 struct EnvFlags {
@@ -891,10 +779,8 @@ int lower_bound_i32(const int32_t *dIndx, const std::vector<int64_t> &beg, const
   return YCNR_OK;
 }
 
-// validate 0 <= indx[i] < limit on the device
-int check_index_range(const int32_t *dIndx, int64_t n, int64_t limit, hipStream_t stream,
-                      const char *what) {
-  if (n == 0) return YCNR_OK;
+// got = {max, min} of the n > 0 column ids on the device
+int index_max_min(const int32_t *dIndx, int64_t n, hipStream_t stream, int32_t got[2]) {
   int32_t *dmm = nullptr;
   HIP_TRY(hipMalloc(&dmm, 2 * sizeof(int32_t)));
   int32_t init[2] = {INT32_MIN, INT32_MAX};
@@ -904,14 +790,34 @@ int check_index_range(const int32_t *dIndx, int64_t n, int64_t limit, hipStream_
     hipLaunchKernelGGL(max_i32_kernel, dim3(blocks), dim3(256), 0, stream, dIndx, n, dmm, dmm + 1);
     e = hipGetLastError();
   }
-  int32_t got[2] = {0, 0};
-  if (e == hipSuccess) e = hipMemcpyAsync(got, dmm, sizeof got, hipMemcpyDeviceToHost, stream);
+  got[0] = got[1] = 0;
+  if (e == hipSuccess) e = hipMemcpyAsync(got, dmm, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, stream);
   if (e == hipSuccess) e = hipStreamSynchronize(stream);
   (void)hipFree(dmm);
   if (e != hipSuccess) return fail(YCNR_ERR_HIP, "index range check failed: %s", hipGetErrorString(e));
+  return YCNR_OK;
+}
+
+// validate 0 <= indx[i] < limit on the device
+int check_index_range(const int32_t *dIndx, int64_t n, int64_t limit, hipStream_t stream,
+                      const char *what) {
+  if (n == 0) return YCNR_OK;
+  int32_t got[2];
+  if (int rc = index_max_min(dIndx, n, stream, got)) return rc;
   if (got[1] < 0 || (int64_t)got[0] >= limit)
     return fail(YCNR_ERR_INVALID, "%s: column id out of range (min %d, max %d, rows of the opposite side %lld)",
                 what, got[1], got[0], (long long)limit);
+  return YCNR_OK;
+}
+
+// the column ids against a half-open range (banded uploads: only this rank's bands may appear)
+int check_index_bounds(const int32_t *dIndx, int64_t n, int64_t lo, int64_t hi, hipStream_t stream, const char *what) {
+  if (n == 0) return YCNR_OK;
+  int32_t got[2];
+  if (int rc = index_max_min(dIndx, n, stream, got)) return rc;
+  if ((int64_t)got[1] < lo || (int64_t)got[0] >= hi)
+    return fail(YCNR_ERR_INVALID, "%s: column id outside this rank's bands (min %d, max %d, bands cover [%lld, %lld))", what, got[1], got[0],
+                (long long)lo, (long long)hi);
   return YCNR_OK;
 }
 
@@ -961,18 +867,14 @@ struct Part {
 
 // A side whose half-step is sharded by BANDS OF COLUMNS (ycnr_als_set_ratings_banded): what the upload leaves besides the
 // side's single Part (local ratings, chunk units, the arena of band + temporary slabs, the owned rows as SplitRow list)
-struct BandedSide {
+struct BandedSide : BandedLayout {
   bool on = false;
   int nBands = 0, world = 1, rank = 0;
   std::vector<int64_t> rankBands, ownerBounds;    // world + 1 band indices / row ids
-  std::vector<int64_t> groupUnit0, groupUnits;     // per owner group: its chunk units [unit0, +n) of the Part's unit list
-  std::vector<int64_t> groupSum0, groupSums;       // ... and its multi-chunk (row, band) segments [sum0, +n) of dSums
-  std::vector<int64_t> groupSlab0;                 // first band slab of group g in the arena (rows of g x local bands)
-  std::vector<int64_t> recvSlab0;                  // first slab of source rank r in dRecv (owned rows x bands of r; own rank: unused)
   SlabSum *dSums = nullptr;
   void *dRecv = nullptr;
   const void **dTable = nullptr;                   // owned rows x nBands slab pointers (null: no rating of the row in that band)
-  int64_t bandSlabs = 0, tmpSlabs = 0, recvSlabs = 0, ownedSolved = 0, nSums = 0;
+  int64_t recvSlabs = 0, ownedSolved = 0, nSums = 0;
   int64_t slabElems = 0;
   hipEvent_t evRecv = nullptr, evStage[kFewSlabs] = {};  // stage s: the group computed in it is complete (on its piece stream)
   void release() {
@@ -1650,7 +1552,15 @@ static int upload_ratings(ycnr_als *h, Ratings &R, int64_t totalRows, int64_t op
   return YCNR_OK;
 }
 
-// Upload + schedule of one piece [rowBegin, rowEnd) of a side's rows into newR / S (both released
+// slabs the arena of the any-k path holds: rows are solved in batches that fit it (a k = 512 float32 image is 541 KB and
+// several MB beyond 1024 factors: a portion of 10 K short rows would ask for gigabytes)
+static int64_t gen_arena_slabs(size_t slabBytes) {
+  int64_t arenaBytes = kGenArenaBytes;
+  if (const char *e = getenv("YCNR_GEN_ARENA_MB")) arenaBytes = (int64_t)std::max(1, atoi(e)) << 20;  // tests force several batches
+  return std::max<int64_t>(1, arenaBytes / (int64_t)slabBytes);
+}
+
+// Upload + schedule (schedule.h) of one piece [rowBegin, rowEnd) of a side's rows into newR / S (both released
 // by the caller when this fails).
 static int build_part(ycnr_als *h, int side, const int64_t *rowPtr, const int32_t *indx, const void *vals, int64_t rowBegin,
                       int64_t rowEnd, int memKind, Ratings &newR, Schedule &S, int64_t sideNnz, int64_t sideSplitNnz) {
@@ -1658,149 +1568,49 @@ static int build_part(ycnr_als *h, int side, const int64_t *rowPtr, const int32_
   int rc = upload_ratings(h, newR, h->rows(side), h->rows(1 - side), rowPtr, indx, vals, rowBegin,
                           rowEnd, memKind, hp, side == YCNR_BY_USER ? "set_ratings(byUser)" : "set_ratings(byItem)");
   if (rc) return rc;
-  std::vector<Unit> units;
-  std::vector<SplitRow> split;
-  int64_t nSlabs = 0, solved = 0;
   const bool gen = is_gen(h->copt.dtype, h->copt.factorsCount);  // any-k path: every primal row through slabs, in row order
   const bool big = !gen && h->copt.factorsCount > kMaxFactors;
+  const size_t slabElems = gen ? (size_t)gen_slab_elems(slab_nb(h->copt.factorsCount))
+                               : big ? (size_t)wg_slab_floats(slab_nb(h->copt.factorsCount)) : (size_t)slab_regs(h->copt, side) * 64;
+  PlanParams P;
+  P.kind = gen ? kAnyK : big ? kWorkgroup : kOneWave;
   // k > 128: a unit is a whole workgroup's work, so chunks are long (a slab is 140 KB at k = 256)
   // (an explicit options.chunkRatings is honoured there too: tests cut short rows into chunks with it)
   // The automatic chunk length follows the split rows of the WHOLE side (sideNnz: their ratings), not of this piece: where a
   // split row is cut decides the order its partial sums are added in, so a length that depended on the piece would make the
   // factors depend on how the rows are cut into shards and pieces (and a feedback re-cut would change them: round-3 review).
-  const int chunkRatings = h->autoChunk ? (gen ? kGenChunk : big ? kWgChunk : auto_chunk(sideNnz, sideSplitNnz)) : h->copt.chunkRatings;
-  if (gen)
-    build_schedule(hp.data(), rowBegin, rowEnd - rowBegin, chunkRatings, units, split, nSlabs, solved, dual_max_ratings(h->copt), 0);
-  else
-    build_schedule(hp.data(), rowBegin, rowEnd - rowBegin, chunkRatings, units, split, nSlabs, solved, -1,
-                   big && h->autoChunk ? kWgFusedMax : std::min(chunkRatings, h->copt.chunkRatings), big ? kMaxSlabsPerRowBig : kMaxSlabsPerRow);
-  int64_t arenaSlabs = nSlabs;
-  // Band-major chunks (unless YCNR_FLAG_NO_BANDS): when the fixed matrix is far larger than the
-  // last-level cache, cut every split row at the same column-id boundaries ("bands" of
-  // kBandBytes of the fixed matrix) instead of every `chunk` ratings, and run the chunks band
-  // by band.  All waves in flight then gather from one band, which stays cache-resident while
-  // each of its rows is used once per rating that refers to it.  Rows are assumed sorted by
-  // column id (they are when they come from a CSR transpose); unsorted rows only lose locality.
+  P.chunk = h->autoChunk ? (gen ? kGenChunk : big ? kWgChunk : auto_chunk(sideNnz, sideSplitNnz)) : h->copt.chunkRatings;
+  P.fusedMax = big && h->autoChunk ? kWgFusedMax : std::min(P.chunk, h->copt.chunkRatings);
+  P.maxSlabs = big ? kMaxSlabsPerRowBig : kMaxSlabsPerRow;
+  P.dualMax = dual_max_ratings(h->copt);
+  P.k = h->opt.factorsCount;
+  static const int order = getenv("YCNR_ROW_ORDER") ? atoi(getenv("YCNR_ROW_ORDER")) : -1;  // 0: whole rows stay sorted (A/B)
+  P.shuffle = order < 0;
+  if (gen) P.arenaSlabs = gen_arena_slabs(slabElems * h->ts());
+  PiecePlan plan = plan_piece(hp.data(), rowBegin, rowEnd - rowBegin, P);
+  // Band-major chunks (schedule.h), unless YCNR_FLAG_NO_BANDS: when the fixed matrix is far larger than the last-level
+  // cache, in bands of kBandBytes of it
   {
     const int64_t fixedRows = h->rows(1 - side);
     const int64_t rowBytes = (int64_t)h->copt.factorsCount * (int64_t)h->ts();
     int64_t bandBytes = kBandBytes;
     if (const char *e = getenv("YCNR_BAND_MB")) bandBytes = (int64_t)atoi(e) << 20;  // per upload, not per half-step: read live (tests set it)
-    if (!big && !gen && nSlabs > 1 && !(h->copt.flags & YCNR_FLAG_NO_BANDS) && bandBytes > 0 && fixedRows * rowBytes > 2 * bandBytes) {
+    if (P.kind == kOneWave && plan.nSlabs > 1 && !(h->copt.flags & YCNR_FLAG_NO_BANDS) && bandBytes > 0 && fixedRows * rowBytes > 2 * bandBytes) {
       // at most kMaxSlabsPerRow / 2 bands, so that a row present in every band still has chunks to
       // spare (very large fixed matrices get wider bands instead of a failed upload)
       const int64_t W = std::max<int64_t>(std::max<int64_t>(1, bandBytes / rowBytes), (fixedRows + kMaxSlabsPerRow / 2 - 1) / (kMaxSlabsPerRow / 2));
       const int nBands = (int)((fixedRows + W - 1) / W);
-      const int64_t base = hp[0];
-      std::vector<int64_t> qBeg, qEnd, cuts;
-      std::vector<int32_t> qKey;
-      for (const SplitRow &sr : split) {
-        const int64_t b = hp[sr.row - rowBegin] - base, e = hp[sr.row - rowBegin + 1] - base;
-        for (int j = 1; j < nBands; ++j) {
-          qBeg.push_back(b);
-          qEnd.push_back(e);
-          qKey.push_back((int32_t)(j * W));
-        }
-      }
-      int rc2 = lower_bound_i32(newR.dIndx, qBeg, qEnd, qKey, cuts, h->stream);
-      if (rc2) return rc2;
-      struct BandUnit { Unit u; int band; };
-      std::vector<BandUnit> bu;
-      const int64_t chunk = chunkRatings, minSeg = std::max<int64_t>(64, chunk / 4);
-      int64_t slabs = 0;
-      for (size_t r = 0; r < split.size(); ++r) {
-        SplitRow &sr = split[r];
-        const int64_t b = hp[sr.row - rowBegin] - base, e = hp[sr.row - rowBegin + 1] - base;
-        // band segments, short ones merged into their successor (the last into its predecessor)
-        std::vector<std::pair<int64_t, int>> seg;  // (start, band); ends at the next start / e
-        int64_t p = b;
-        for (int j = 0; j < nBands; ++j) {
-          const int64_t q = j + 1 < nBands ? std::min(e, std::max(p, cuts[r * (size_t)(nBands - 1) + j])) : e;
-          if (q - p >= minSeg) {
-            seg.push_back({p, j});
-            p = q;
-          }
-        }
-        if (seg.empty()) seg.push_back({b, 0});
-        seg[0].first = b;  // ratings left over before the first kept boundary join the first segment
-        int64_t ch = chunk;
-        const int64_t room = kMaxSlabsPerRow - (int64_t)seg.size();
-        if (room < 1 || (sr.n + ch - 1) / ch > room) ch = std::max(ch, (sr.n + std::max<int64_t>(1, room) - 1) / std::max<int64_t>(1, room));
-        sr.slab0 = (int32_t)slabs;
-        int32_t parts = 0;
-        for (size_t i = 0; i < seg.size(); ++i) {
-          const int64_t sb = seg[i].first, se = i + 1 < seg.size() ? seg[i + 1].first : e, len = se - sb;
-          const int64_t np = (len + ch - 1) / ch;
-          const int64_t pl = (((len + np - 1) / np) + 3) & ~(int64_t)3;
-          for (int64_t q = 0; q < np; ++q) {
-            const int64_t ub = sb + q * pl, ue = std::min(se, ub + pl);
-            if (ue <= ub) break;
-            bu.push_back({Unit{ub, ue, sr.row, (int32_t)(slabs + parts)}, seg[i].second});
-            ++parts;
-          }
-        }
-        if (parts > kMaxSlabsPerRow) return fail(YCNR_ERR_STATE, "band schedule: %d chunks for row %d", parts, sr.row);
-        sr.nslabs = parts;
-        slabs += parts;
-      }
-      std::stable_sort(bu.begin(), bu.end(), [](const BandUnit &x, const BandUnit &y) {
-        return x.band != y.band ? x.band < y.band : (x.u.end - x.u.beg) > (y.u.end - y.u.beg);
-      });
-      std::vector<Unit> all;
-      all.reserve(bu.size() + units.size() - (size_t)nSlabs);
-      for (const BandUnit &x : bu) all.push_back(x.u);
-      all.insert(all.end(), units.begin() + nSlabs, units.end());
-      units.swap(all);
-      nSlabs = slabs;
-      arenaSlabs = slabs;
+      const BoundQueries q = band_queries(plan, hp.data(), rowBegin, W, nBands);
+      std::vector<int64_t> cuts;
+      if (int rc2 = lower_bound_i32(newR.dIndx, q.beg, q.end, q.key, cuts, h->stream)) return rc2;
+      const BandCutError bad = band_recut(plan, hp.data(), rowBegin, P, nBands, cuts);
+      if (bad.parts) return fail(YCNR_ERR_STATE, "band schedule: %d chunks for row %d", bad.parts, bad.row);
     }
   }
-  S.nUnits = (int64_t)units.size();
-  S.nSplit = (int64_t)split.size();
-  S.maxRowSlabs = 0;
-  for (const SplitRow &sr : split) S.maxRowSlabs = std::max(S.maxRowSlabs, sr.nslabs);
-  S.nSlabs = nSlabs;
-  S.solvedRows = solved;
-  S.fusedRatings = 0;
-  for (size_t i = (size_t)nSlabs; i < units.size(); ++i) S.fusedRatings += units[i].end - units[i].beg;
-  // whole rows are sorted by descending length: rows short enough for the dual form are the
-  // tail of the list, grouped by their number of 16-rating blocks
-  const int dualMax = dual_max_ratings(h->copt);
-  S.nPrimal = 0;
-  for (size_t i = (size_t)nSlabs; i < units.size(); ++i) {
-    const int64_t n = units[i].end - units[i].beg;
-    if (n > dualMax) {
-      ++S.nPrimal;
-      continue;
-    }
-    const int m = (int)((n + 15) / 16);
-    if (S.dualCount[m] == 0) S.dualFirst[m] = (int64_t)i;
-    ++S.dualCount[m];
-    ++S.dualRows;
-    S.dualRatings += n;
-    const double nd = (double)n, kd = (double)h->opt.factorsCount;
-    S.dualFlops += nd * (nd + 1) * kd + nd * nd * nd / 3.0 + 2.0 * nd * nd + 2.0 * nd * kd;
-  }
-  // Launch order of the whole rows in primal form (k <= 128: one wave per row).  Sorted by descending length, the waves that
-  // share a SIMD at any moment work on rows of the same length that started together and go through their Gramian phase (matrix
-  // pipe) and their solve phase (vector ALU) side by side.  A large launch therefore takes its rows in a fixed pseudo-random
-  // order -- neighbours in launch order differ in length and drift apart -- with the shortest rows kept, sorted, for the tail:
-  // MAL-scale user half-step 12.18 -> 11.95 ms (interleaved A/B, two runs each; profiles/r05_ab.sh).  Every row is solved by
-  // its own wave: the order cannot change a result.  YCNR_ROW_ORDER=0: sorted (A/B).  Riffles of the sorted list (position q i + j
-  // takes row i + j N / q) were measured much SLOWER for q = 2 ... 32 (12.5 ... 19.4 ms): the dispatcher deals workgroups to
-  // the XCDs round-robin, so part j of the list -- and all the long rows -- landed on XCD j mod 8.
-  constexpr int64_t kShuffleMinRows = 16384;
-  if (!big && !gen && S.nPrimal >= kShuffleMinRows) {
-    static const int order = getenv("YCNR_ROW_ORDER") ? atoi(getenv("YCNR_ROW_ORDER")) : -1;
-    if (order < 0) {
-      const int64_t tail = std::min<int64_t>(S.nPrimal / 8, 8192);  // the shortest rows stay where they are
-      uint64_t x = 0x9E3779B97F4A7C15ull;
-      for (int64_t i = S.nPrimal - tail - 1; i > 0; --i) {
-        x ^= x << 13; x ^= x >> 7; x ^= x << 17;
-        std::swap(units[(size_t)(nSlabs + i)], units[(size_t)(nSlabs + (int64_t)(x % (uint64_t)(i + 1)))]);
-      }
-    }
-  }
+  static_cast<PlanCounts &>(S) = plan;
+  S.nUnits = (int64_t)plan.units.size();
+  S.nSplit = (int64_t)plan.split.size();
+  S.genBatches.swap(plan.genBatches);
   if (big && slab_nb(h->copt.factorsCount) == kPairNB && S.nPrimal > 0 && !env_flags().noPair) {
     int64_t batchRows = kPairBatchRows;
     if (const char *e = getenv("YCNR_PAIR_BATCH_ROWS")) batchRows = std::max(256, atoi(e));  // read per upload
@@ -1808,31 +1618,17 @@ static int build_part(ycnr_als *h, int side, const int64_t *rowPtr, const int32_
     HIP_TRY(hipMalloc(&S.dRowSlabs, (size_t)S.rowSlabRows * (size_t)wg_slab_floats(kPairNB) * sizeof(float)));
   }
   if (S.nUnits) {
-    HIP_TRY(hipMalloc(&S.dUnits, sizeof(Unit) * units.size()));
-    HIP_TRY(hipMemcpy(S.dUnits, units.data(), sizeof(Unit) * units.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMalloc(&S.dUnits, sizeof(Unit) * plan.units.size()));
+    HIP_TRY(hipMemcpy(S.dUnits, plan.units.data(), sizeof(Unit) * plan.units.size(), hipMemcpyHostToDevice));
   }
   if (S.nSplit) {
-    // the reduce kernel takes the rows in this order, one wave each: rows with the most slabs first, so that
-    // the 64-slab rows of the most popular items do not start when everything else has finished
-    if (!big && !gen)
-      std::stable_sort(split.begin(), split.end(), [](const SplitRow &x, const SplitRow &y) { return x.nslabs > y.nslabs; });
-    HIP_TRY(hipMalloc(&S.dSplit, sizeof(SplitRow) * split.size()));
-    HIP_TRY(hipMemcpy(S.dSplit, split.data(), sizeof(SplitRow) * split.size(), hipMemcpyHostToDevice));
-    const size_t slabElems = gen ? (size_t)gen_slab_elems(slab_nb(h->copt.factorsCount))
-                                 : big ? (size_t)wg_slab_floats(slab_nb(h->copt.factorsCount)) : (size_t)slab_regs(h->copt, side) * 64;
-    if (gen) {
-      // rows are solved in batches whose slabs fit the arena (a k = 512 float32 image is 541 KB)
-      int64_t arenaBytes = kGenArenaBytes;
-      if (const char *e = getenv("YCNR_GEN_ARENA_MB")) arenaBytes = (int64_t)std::max(1, atoi(e)) << 20;  // tests force several batches
-      const int64_t fit = std::max<int64_t>(1, arenaBytes / (int64_t)(slabElems * h->ts()));
-      S.genBatches = gen_batches(split, fit);
-      arenaSlabs = 0;
-      for (const GenBatch &b : S.genBatches) arenaSlabs = std::max<int64_t>(arenaSlabs, b.nSlabs);
-    }
-    HIP_TRY(hipMalloc(&S.dSlabs, (size_t)arenaSlabs * slabElems * h->ts()));
+    HIP_TRY(hipMalloc(&S.dSplit, sizeof(SplitRow) * plan.split.size()));
+    HIP_TRY(hipMemcpy(S.dSplit, plan.split.data(), sizeof(SplitRow) * plan.split.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMalloc(&S.dSlabs, (size_t)S.arenaSlabs * slabElems * h->ts()));
   }
   return YCNR_OK;
 }
+
 
 // nParts pieces [b[i], b[i + 1]) of this rank's rows.  Everything is built in locals and committed
 // together at the end: a failure on the way leaves the handle's previous upload (or none) intact,
@@ -1853,7 +1649,7 @@ static int set_ratings_parts(ycnr_als *h, int side, const int64_t *rowPtr, const
   // ratings (-> 3072), a few per cent of the user side's (-> 1024: its chunk kernel is a few hundred waves whose length is
   // the kernel's; with the item side's 3072 it was a 300 us chain in front of every piece's row kernel).
   if (!rowPtr) return fail(YCNR_ERR_INVALID, "set_ratings: null rowPtr");
-  int64_t sideNnz = 0, sideSplitNnz = 0;
+  SideNnz sideNnz;
   if (h->autoChunk) {
     const int64_t nr = h->rows(side);
     std::vector<int64_t> whole;
@@ -1863,17 +1659,13 @@ static int set_ratings_parts(ycnr_als *h, int side, const int64_t *rowPtr, const
       HIP_TRY(hipMemcpy(whole.data(), rowPtr, sizeof(int64_t) * ((size_t)nr + 1), hipMemcpyDeviceToHost));
       rp = whole.data();
     }
-    for (int64_t r = 0; r < nr; ++r) {
-      const int64_t n = rp[r + 1] - rp[r];
-      sideNnz += n > 0 ? n : 0;
-      if (n > kDefaultChunk) sideSplitNnz += n;
-    }
+    sideNnz = side_nnz(rp, nr);
   }
   for (int i = 0; i < nParts; ++i) {
     Part &p = pend.parts[(size_t)i];
     hipError_t e = p.create_events();
     if (e != hipSuccess) return fail(YCNR_ERR_HIP, "set_ratings: hipEventCreate: %s", hipGetErrorString(e));
-    int rc = build_part(h, side, rowPtr, indx, vals, b[i], b[i + 1], memKind, p.R, p.S, sideNnz, sideSplitNnz);
+    int rc = build_part(h, side, rowPtr, indx, vals, b[i], b[i + 1], memKind, p.R, p.S, sideNnz.nnz, sideNnz.splitNnz);
     if (rc) return rc;
   }
   HIP_TRY(hipStreamSynchronize(h->stream));  // nothing in flight still reads the previous upload
@@ -1938,29 +1730,6 @@ int ycnr_als_set_ratings_sharded(ycnr_als *h, int side, const int64_t *rowPtr, c
   return rc;
 }
 
-// min / max of the column ids against a half-open range (banded uploads: only this rank's bands may appear)
-static int check_index_bounds(const int32_t *dIndx, int64_t n, int64_t lo, int64_t hi, hipStream_t stream, const char *what) {
-  if (n == 0) return YCNR_OK;
-  int32_t *dmm = nullptr;
-  HIP_TRY(hipMalloc(&dmm, 2 * sizeof(int32_t)));
-  int32_t init[2] = {INT32_MIN, INT32_MAX};
-  hipError_t e = hipMemcpyAsync(dmm, init, sizeof init, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess) {
-    const int blocks = (int)std::min<int64_t>(2048, (n + 255) / 256);
-    hipLaunchKernelGGL(max_i32_kernel, dim3(blocks), dim3(256), 0, stream, dIndx, n, dmm, dmm + 1);
-    e = hipGetLastError();
-  }
-  int32_t got[2] = {0, 0};
-  if (e == hipSuccess) e = hipMemcpyAsync(got, dmm, sizeof got, hipMemcpyDeviceToHost, stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  (void)hipFree(dmm);
-  if (e != hipSuccess) return fail(YCNR_ERR_HIP, "index range check failed: %s", hipGetErrorString(e));
-  if ((int64_t)got[1] < lo || (int64_t)got[0] >= hi)
-    return fail(YCNR_ERR_INVALID, "%s: column id outside this rank's bands (min %d, max %d, bands cover [%lld, %lld))", what, got[1], got[0],
-                (long long)lo, (long long)hi);
-  return YCNR_OK;
-}
-
 int ycnr_als_set_ratings_banded(ycnr_als *h, int side, const int64_t *rowPtr, const int32_t *indx, const void *vals, int memKind,
                                 int nBands, const int64_t *bandBounds, const int64_t *rankBands, const int64_t *ownerBounds) {
   if (!h || !bandBounds || !rankBands || !ownerBounds) return fail(YCNR_ERR_INVALID, "null argument");
@@ -2014,19 +1783,13 @@ int ycnr_als_set_ratings_banded(ycnr_als *h, int side, const int64_t *rowPtr, co
       if (int r2 = check_index_bounds(part.R.dIndx, part.R.nnz, bandBounds[bl], bandBounds[bh], h->stream, "set_ratings_banded")) return r2;
     // where every row's ratings cross this rank's inner band boundaries (rows are sorted by column id)
     const int64_t base = hp[0];
-    std::vector<int64_t> qBeg, qEnd, cuts;
-    std::vector<int32_t> qKey;
-    std::vector<int64_t> qRow;
-    for (int64_t r = 0; r < rows; ++r) {
-      if (hp[r + 1] == hp[r]) continue;
-      qRow.push_back(r);
-      for (int b = bl + 1; b < bh; ++b) {
-        qBeg.push_back(hp[r] - base);
-        qEnd.push_back(hp[r + 1] - base);
-        qKey.push_back((int32_t)bandBounds[b]);
-      }
-    }
-    if (int r3 = lower_bound_i32(part.R.dIndx, qBeg, qEnd, qKey, cuts, h->stream)) return r3;
+    std::vector<int64_t> qRow, cuts;
+    std::vector<int32_t> keys;
+    for (int64_t r = 0; r < rows; ++r)
+      if (hp[r + 1] != hp[r]) qRow.push_back(r);
+    for (int b = bl + 1; b < bh; ++b) keys.push_back((int32_t)bandBounds[b]);
+    const BoundQueries q = bound_queries(hp.data(), qRow, keys);
+    if (int r3 = lower_bound_i32(part.R.dIndx, q.beg, q.end, q.key, cuts, h->stream)) return r3;
     for (size_t i = 0; i < qRow.size(); ++i) {
       const int64_t r = qRow[i];
       int64_t p = hp[r] - base;
@@ -2049,126 +1812,55 @@ int ycnr_als_set_ratings_banded(ycnr_als *h, int side, const int64_t *rowPtr, co
     else rc = rca;
   }
   auto finish = [&]() -> int {
-    int64_t sideNnz = 0, sideSplitNnz = 0;
-    std::vector<int64_t> rowTotal((size_t)rows, 0);
+    // the side's row pointer, from the agreed counts.  One rank of an emulated world never sees the counts of the other
+    // ranks' bands: it sizes the chunks for a side `world` times its own share, as the real run would
+    std::vector<int64_t> sidePtr((size_t)rows + 1, 0);
     for (int64_t r = 0; r < rows; ++r) {
       int64_t t = 0;
       for (int b = 0; b < nBands; ++b) t += (int64_t)counts[(size_t)r * nBands + b];
-      rowTotal[(size_t)r] = t;
-      sideNnz += t;
-      if (t > kDefaultChunk) sideSplitNnz += t;
+      sidePtr[(size_t)r + 1] = sidePtr[(size_t)r] + t;
     }
-    if (h->comm.active() && h->comm.transport == YCNR_COMM_STUB) {
-      // (one rank of an emulated world: the counts of the other ranks' bands never arrive; size the chunks for a side `world`
-      // times this rank's share, as the real run would)
-      sideNnz = 0;
-      sideSplitNnz = 0;
-      for (int64_t r = 0; r < rows; ++r) {
-        const int64_t t = rowTotal[(size_t)r] * world;
-        sideNnz += t;
-        if (t > kDefaultChunk) sideSplitNnz += t;
-      }
-    }
-    const int64_t chunk = h->autoChunk ? auto_chunk(sideNnz, sideSplitNnz) : h->copt.chunkRatings;
+    const SideNnz sn = side_nnz(sidePtr.data(), rows, h->comm.active() && h->comm.transport == YCNR_COMM_STUB ? world : 1);
+    const int64_t chunk = h->autoChunk ? auto_chunk(sn.nnz, sn.splitNnz) : h->copt.chunkRatings;
     B.nBands = nBands;
     B.world = world;
     B.rank = rank;
     B.rankBands.assign(rankBands, rankBands + world + 1);
     B.ownerBounds.assign(ownerBounds, ownerBounds + world + 1);
     B.slabElems = (int64_t)slab_regs(h->copt, side) * 64;
-    B.groupSlab0.assign((size_t)world + 1, 0);
-    for (int g = 0; g < world; ++g) B.groupSlab0[(size_t)g + 1] = B.groupSlab0[(size_t)g] + (ownerBounds[g + 1] - ownerBounds[g]) * bpr;
-    B.bandSlabs = B.groupSlab0[(size_t)world];
-    // units: group by group (the order they are computed and sent in), longest first inside a group
-    const int64_t base = hp[0];
-    std::vector<Unit> units;
-    std::vector<SlabSum> sums;
-    B.groupUnit0.assign((size_t)world, 0);
-    B.groupUnits.assign((size_t)world, 0);
-    B.groupSum0.assign((size_t)world, 0);
-    B.groupSums.assign((size_t)world, 0);
-    int64_t tmp = 0;
-    for (int st = 1; st <= world; ++st) {  // in the order the groups are computed and sent: consecutive stages are contiguous
-      const int g = (rank + st) % world;
-      B.groupUnit0[(size_t)g] = (int64_t)units.size();
-      B.groupSum0[(size_t)g] = (int64_t)sums.size();
-      const size_t u0 = units.size();
-      for (int64_t r = ownerBounds[g]; r < ownerBounds[g + 1]; ++r) {
-        if (hp[r + 1] == hp[r]) continue;
-        int64_t p = hp[r] - base;
-        for (int j = 0; j < bpr; ++j) {
-          const int64_t len = (int64_t)counts[(size_t)r * nBands + (size_t)(bl + j)];
-          if (len <= 0) continue;
-          const int64_t bandSlab = B.groupSlab0[(size_t)g] + (r - ownerBounds[g]) * bpr + j;
-          const int64_t np = (len + chunk - 1) / chunk, pl = (((len + np - 1) / np) + 3) & ~(int64_t)3;
-          if (np == 1) {
-            units.push_back(Unit{p, p + len, (int32_t)r, (int32_t)bandSlab});
-          } else {
-            int64_t made = 0;
-            for (int64_t q = 0; q < np; ++q) {
-              const int64_t ub = p + q * pl, ue = std::min(p + len, ub + pl);
-              if (ue <= ub) break;
-              units.push_back(Unit{ub, ue, (int32_t)r, (int32_t)(B.bandSlabs + tmp + made)});
-              ++made;
-            }
-            sums.push_back(SlabSum{bandSlab * B.slabElems, (B.bandSlabs + tmp) * B.slabElems, (int32_t)made, 0});
-            tmp += made;
-          }
-          p += len;
-        }
-      }
-      std::stable_sort(units.begin() + (ptrdiff_t)u0, units.end(), [](const Unit &x, const Unit &y) { return (x.end - x.beg) > (y.end - y.beg); });
-      B.groupUnits[(size_t)g] = (int64_t)units.size() - B.groupUnit0[(size_t)g];
-      B.groupSums[(size_t)g] = (int64_t)sums.size() - B.groupSum0[(size_t)g];
-    }
-    B.tmpSlabs = tmp;
-    B.nSums = (int64_t)sums.size();
-    if (B.bandSlabs + B.tmpSlabs > 0x7fffffffLL) return fail(YCNR_ERR_UNSUPPORTED, "set_ratings_banded: too many slabs");
-    Schedule &S = part.S;
-    S.nUnits = (int64_t)units.size();
-    S.nSlabs = S.nUnits;
-    if (S.nUnits) {
-      HIP_TRY(hipMalloc(&S.dUnits, sizeof(Unit) * units.size()));
-      HIP_TRY(hipMemcpy(S.dUnits, units.data(), sizeof(Unit) * units.size(), hipMemcpyHostToDevice));
-    }
-    if (B.nSums) {
-      HIP_TRY(hipMalloc(&B.dSums, sizeof(SlabSum) * sums.size()));
-      HIP_TRY(hipMemcpy(B.dSums, sums.data(), sizeof(SlabSum) * sums.size(), hipMemcpyHostToDevice));
-    }
-    HIP_TRY(hipMalloc(&S.dSlabs, std::max<size_t>((size_t)(B.bandSlabs + B.tmpSlabs) * (size_t)B.slabElems * ts, 64)));
-    // what this rank owns: its rows' band slabs from every rank, and the rows to solve
-    const int64_t own0 = ownerBounds[rank], ownN = ownerBounds[rank + 1] - own0;
-    B.recvSlab0.assign((size_t)world + 1, 0);
-    for (int r = 0; r < world; ++r)
-      B.recvSlab0[(size_t)r + 1] = B.recvSlab0[(size_t)r] + (r == rank ? 0 : ownN * (rankBands[r + 1] - rankBands[r]));
+    BandedPlan plan = plan_banded(hp.data(), counts.data(), nBands, rankBands, ownerBounds, rank, world, chunk, B.slabElems);
+    if (plan.error) return fail(YCNR_ERR_UNSUPPORTED, "set_ratings_banded: %s", plan.error);
+    static_cast<BandedLayout &>(B) = plan;
+    B.nSums = (int64_t)plan.sums.size();
     B.recvSlabs = B.recvSlab0[(size_t)world];
-    HIP_TRY(hipMalloc(&B.dRecv, std::max<size_t>((size_t)B.recvSlabs * (size_t)B.slabElems * ts, 64)));
-    HIP_TRY(hipMemset(B.dRecv, 0, std::max<size_t>((size_t)B.recvSlabs * (size_t)B.slabElems * ts, 64)));
-    std::vector<const void *> table((size_t)ownN * (size_t)nBands, nullptr);
-    std::vector<SplitRow> owned;
-    const size_t slabBytes = (size_t)B.slabElems * ts;
-    for (int64_t i = 0; i < ownN; ++i) {
-      const int64_t r = own0 + i;
-      if (rowTotal[(size_t)r] <= 0) continue;
-      owned.push_back(SplitRow{rowTotal[(size_t)r], (int32_t)r, (int32_t)(i * nBands), (int32_t)nBands, 0});
-      for (int b = 0; b < nBands; ++b) {
-        if (counts[(size_t)r * nBands + b] <= 0) continue;
-        int src = 0;
-        while (src + 1 < world && b >= rankBands[src + 1]) ++src;
-        const char *p = src == rank ? (const char *)S.dSlabs + (size_t)(B.groupSlab0[(size_t)rank] + i * bpr + (b - bl)) * slabBytes
-                                    : (const char *)B.dRecv + (size_t)(B.recvSlab0[(size_t)src] + i * (rankBands[src + 1] - rankBands[src]) + (b - rankBands[src])) * slabBytes;
-        table[(size_t)i * nBands + b] = p;
-      }
-    }
-    if (owned.size() > 0x7fffffffULL / (size_t)std::max(nBands, 1)) return fail(YCNR_ERR_UNSUPPORTED, "set_ratings_banded: too many owned rows");
-    S.nSplit = (int64_t)owned.size();
+    Schedule &S = part.S;
+    S.nUnits = (int64_t)plan.units.size();
+    S.nSlabs = S.nUnits;
+    S.nSplit = (int64_t)plan.owned.size();
     S.solvedRows = S.nSplit;
     S.maxRowSlabs = nBands;
     B.ownedSolved = S.nSplit;
-    if (S.nSplit) {
-      HIP_TRY(hipMalloc(&S.dSplit, sizeof(SplitRow) * owned.size()));
-      HIP_TRY(hipMemcpy(S.dSplit, owned.data(), sizeof(SplitRow) * owned.size(), hipMemcpyHostToDevice));
+    if (S.nUnits) {
+      HIP_TRY(hipMalloc(&S.dUnits, sizeof(Unit) * plan.units.size()));
+      HIP_TRY(hipMemcpy(S.dUnits, plan.units.data(), sizeof(Unit) * plan.units.size(), hipMemcpyHostToDevice));
     }
+    if (B.nSums) {
+      HIP_TRY(hipMalloc(&B.dSums, sizeof(SlabSum) * plan.sums.size()));
+      HIP_TRY(hipMemcpy(B.dSums, plan.sums.data(), sizeof(SlabSum) * plan.sums.size(), hipMemcpyHostToDevice));
+    }
+    if (S.nSplit) {
+      HIP_TRY(hipMalloc(&S.dSplit, sizeof(SplitRow) * plan.owned.size()));
+      HIP_TRY(hipMemcpy(S.dSplit, plan.owned.data(), sizeof(SplitRow) * plan.owned.size(), hipMemcpyHostToDevice));
+    }
+    const size_t slabBytes = (size_t)B.slabElems * ts;
+    HIP_TRY(hipMalloc(&S.dSlabs, std::max<size_t>((size_t)(B.bandSlabs + B.tmpSlabs) * slabBytes, 64)));
+    HIP_TRY(hipMalloc(&B.dRecv, std::max<size_t>((size_t)B.recvSlabs * slabBytes, 64)));
+    HIP_TRY(hipMemset(B.dRecv, 0, std::max<size_t>((size_t)B.recvSlabs * slabBytes, 64)));
+    // the owners' table as pointers: a rank's own band slabs are in its arena, the other ranks' arrive in dRecv
+    std::vector<const void *> table(plan.table.size(), nullptr);
+    for (size_t i = 0; i < table.size(); ++i)
+      if (plan.table[i].src >= 0)
+        table[i] = (const char *)(plan.table[i].src == rank ? S.dSlabs : B.dRecv) + (size_t)plan.table[i].slab * slabBytes;
     HIP_TRY(hipMalloc((void **)&B.dTable, std::max<size_t>(sizeof(void *) * table.size(), 64)));
     if (!table.empty()) HIP_TRY(hipMemcpy((void *)B.dTable, table.data(), sizeof(void *) * table.size(), hipMemcpyHostToDevice));
     B.on = true;
@@ -3351,14 +3043,21 @@ int64_t als_calc_portion(double lambda, int k, const int32_t *alsRows, const int
       uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
     }
   }
-  std::vector<Unit> units;
-  std::vector<SplitRow> split;
-  int64_t nSlabs = 0, solved = 0;
-  build_schedule(rowPtr.data(), 0, nRows, gen ? kGenChunk : big ? kWgChunk : kDefaultChunk, units, split, nSlabs, solved, gen ? 0 : -1,
-                 big ? kWgFusedMax : 0);
-
   const int nb = slab_nb(k);
   const size_t slabElems = gen ? (size_t)gen_slab_elems(nb) : big ? (size_t)wg_slab_floats(nb) : (size_t)slab_elems(nb);
+  // the plan of a piece of the resident trainer (build_part) with every row in primal form and the split rows in row order;
+  // any-k path: solved in batches whose images fit the arena
+  PlanParams P;
+  P.kind = gen ? kAnyK : big ? kWorkgroup : kOneWave;
+  P.chunk = gen ? kGenChunk : big ? kWgChunk : kDefaultChunk;
+  P.fusedMax = big ? kWgFusedMax : 0;
+  P.k = k;
+  P.shuffle = P.sortSplit = false;
+  if (gen) P.arenaSlabs = gen_arena_slabs(slabElems * sizeof(T));
+  const PiecePlan plan = plan_piece(rowPtr.data(), 0, nRows, P);
+  const std::vector<Unit> &units = plan.units;
+  const std::vector<SplitRow> &split = plan.split;
+  const int64_t nSlabs = plan.nSlabs;
 #define L1_TRY(expr)                                                                                  \
   do {                                                                                                \
     hipError_t e_ = (expr);                                                                           \
@@ -3377,18 +3076,7 @@ int64_t als_calc_portion(double lambda, int k, const int32_t *alsRows, const int
   const size_t ioBytes = al(oFixed + (pinned ? 0 : sizeof(T) * uniq.size() * (size_t)k));
   L1_TRY(C.io.reserve(ioBytes));
   L1_TRY(C.reserve_host(ioBytes));
-  // any-k path: rows are solved in batches whose images fit the arena, as in the resident trainer (build_part) -- one
-  // image is 541 KB at k = 512 and several MB beyond 1024 factors, a portion of 10 K short rows would ask for gigabytes
-  std::vector<GenBatch> genBatches;
-  int64_t arenaSlabs = nSlabs;
-  if (gen) {
-    int64_t arenaBytes = kGenArenaBytes;
-    if (const char *e = getenv("YCNR_GEN_ARENA_MB")) arenaBytes = (int64_t)std::max(1, atoi(e)) << 20;  // tests force several batches
-    genBatches = gen_batches(split, std::max<int64_t>(1, arenaBytes / (int64_t)(slabElems * sizeof(T))));
-    arenaSlabs = 0;
-    for (const GenBatch &b : genBatches) arenaSlabs = std::max<int64_t>(arenaSlabs, b.nSlabs);
-  }
-  L1_TRY(C.slabs.reserve(sizeof(T) * std::max<size_t>(1, (size_t)arenaSlabs * slabElems)));
+  L1_TRY(C.slabs.reserve(sizeof(T) * std::max<size_t>(1, (size_t)plan.arenaSlabs * slabElems)));
   char *hb = (char *)C.hostIo, *db = (char *)C.io.p;
   memset(hb + oErr, 0, sizeof(ErrInfo));
   if (!units.empty()) memcpy(hb + oUnits, units.data(), sizeof(Unit) * units.size());
@@ -3416,7 +3104,7 @@ int64_t als_calc_portion(double lambda, int k, const int32_t *alsRows, const int
     StepArgs<T> a{(const Unit *)(db + oUnits), (const SplitRow *)(db + oSplit), (const int32_t *)(db + oIndx), (const T *)(db + oVals), dFixed, dZeros,
                   (T *)(db + oSolved), (T *)C.slabs.p, dErr, lambda, k, 0, 0, 0u};
     if (gen) {
-      rc = launch_step_gen<T>(a, genBatches, stream, nullptr, DualPlan());
+      rc = launch_step_gen<T>(a, plan.genBatches, stream, nullptr, DualPlan());
     } else if constexpr (std::is_same<T, float>::value) {
       if (big) rc = launch_step_big(a, (int64_t)units.size(), nSlabs, (int64_t)split.size(), stream, nullptr, DualPlan());
       else rc = launch_step<T>(a, (int64_t)units.size(), nSlabs, (int64_t)split.size(), stream, nullptr);
