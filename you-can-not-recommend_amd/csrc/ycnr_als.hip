@@ -6,6 +6,7 @@
 // a HIP device every entry point fails with YCNR_ERR_HIP.
 #include "../../include/ycnr_als.h"
 #include "als_kernels.hip.h"
+#include "kernel_choice.h"
 #include "als_wg_kernels.hip.h"
 #include "als_pair_kernels.hip.h"
 #ifdef YCNR_WITH_G32  // devtest build only (make EXTRA=-DYCNR_WITH_G32): the 32 x 32 Gramian kernel of round 3, measured equal
@@ -188,12 +189,6 @@ struct DualPlan {
   // replayed (ycnr_als_step_async), so the forks and joins cost nothing per half-step.
   hipStream_t slabStream = nullptr;
   hipEvent_t slabJoin = nullptr;
-  // The item half-step sharded by user bands (step_banded) borrows the kernel choice of launch_nbe: 1 = the chunk kernel alone
-  // over units [0, nSplitUnits) of args.units; 2 = als_band_reduce_solve_kernel alone over nSplit rows of args.split, whose band
-  // slabs are found through this pointer table
-  int only = 0;
-  const void *const *bandSlab = nullptr;
-  int nBands = 0;
 };
 
 template <int M>
@@ -232,120 +227,102 @@ void launch_rmse(const RmseArgs<T> &a, int nPieces, hipStream_t stream) {
   hipLaunchKernelGGL(kr, dim3((unsigned)nPieces), dim3(256), 0, stream, a);
 }
 
-template <typename T>
-int launch_duals(const StepArgs<T> &, const DualPlan &, hipStream_t) { return YCNR_OK; }
-template <>
-int launch_duals<float>(const StepArgs<float> &args, const DualPlan &dp, hipStream_t stream) {
-  int rc = launch_dual<12>(args, dp, stream);
-  if (!rc) rc = launch_dual<11>(args, dp, stream);
-  if (!rc) rc = launch_dual<10>(args, dp, stream);
-  if (!rc) rc = launch_dual<9>(args, dp, stream);
-  if (!rc) rc = launch_dual<8>(args, dp, stream);
-  if (!rc) rc = launch_dual<7>(args, dp, stream);
-  if (!rc) rc = launch_dual<6>(args, dp, stream);
-  if (!rc) rc = launch_dual<5>(args, dp, stream);
-  if (!rc) rc = launch_dual<4>(args, dp, stream);
-  if (!rc) rc = launch_dual<3>(args, dp, stream);
-  if (!rc) rc = launch_dual<2>(args, dp, stream);
-  if (!rc) rc = launch_dual<1>(args, dp, stream);
-  return rc;
+// the dual classes M, M - 1, ..., 1, in this order (the round-robin over the side streams depends on it); float32 only
+template <typename T, int M = kMaxDualBlocks>
+int launch_duals(const StepArgs<T> &args, const DualPlan &dp, hipStream_t stream) {
+  if constexpr (std::is_same<T, float>::value && M > 0) {
+    if (int rc = launch_dual<M>(args, dp, stream)) return rc;
+    return launch_duals<T, M - 1>(args, dp, stream);
+  }
+  return YCNR_OK;
 }
 
-template <typename T, int NB>
-void (*slab_x6_kernel())(StepArgs<T>) { return nullptr; }
-#define YCNR_X6(NBV) \
-  template <>        \
-  void (*slab_x6_kernel<float, NBV>())(StepArgs<float>) { return als_gram_slab_x6_kernel<NBV>; }
-YCNR_X6(1) YCNR_X6(2) YCNR_X6(3) YCNR_X6(4) YCNR_X6(5) YCNR_X6(6) YCNR_X6(7) YCNR_X6(8)
-#undef YCNR_X6
+// The dual classes next to the row kernel: the side streams wait for dp.fork (which the caller has recorded), take the classes
+// in turn and record their joins; join_duals makes `stream` wait for them.
+template <typename T>
+int fork_duals(const StepArgs<T> &args, const DualPlan &dp, hipStream_t stream) {
+  for (int i = 0; i < dp.nSide; ++i) HIP_TRY(hipStreamWaitEvent(dp.side[i], dp.fork, 0));
+  dp.nextSide = 0;
+  if (int rc = launch_duals<T>(args, dp, stream)) return rc;
+  for (int i = 0; i < dp.nSide; ++i) HIP_TRY(hipEventRecord(dp.join[i], dp.side[i]));
+  return YCNR_OK;
+}
+int join_duals(const DualPlan &dp, hipStream_t stream) {
+  for (int i = 0; i < dp.nSide; ++i) HIP_TRY(hipStreamWaitEvent(stream, dp.join[i], 0));
+  return YCNR_OK;
+}
 
-// k = 16 (NB - 1) + 4: the last block's planes packed into one operand (GramX6D's PK3); YCNR_NO_PK3=1 for A/B runs
-template <int NB>
-bool pk3_k(int k) { return k == 16 * (NB - 1) + 4 && !env_flags().noPk3; }
+// a runtime bool as a template argument: f(std::true_type()) or f(std::false_type()); CAN = false: there is no true form
+template <bool CAN, typename F>
+auto with_bool(bool b, F f) {
+  if constexpr (CAN)
+    if (b) return f(std::true_type());
+  return f(std::false_type());
+}
+// f(std::integral_constant<int, nb>()) for LO <= nb <= HI; false: nb is outside
+template <int LO, int HI, typename F>
+bool dispatch_nb(int nb, F &&f) {
+  if constexpr (LO <= HI) return nb == LO ? (f(std::integral_constant<int, LO>()), true) : dispatch_nb<LO + 1, HI>(nb, f);
+  else return false;
+}
 
-// the same Gramian with the gather staged through LDS by LDS-DMA: two waves per SIMD up to k = 112, one from 116 to 128 (round 4:
-// these eight-block sizes used to fall to the float32-MFMA kernels -- MAL shape, k = 128: 58.9 ms per iteration against 23.4 at k = 112)
-template <typename T, int NB>
-void (*slab_x6d_kernel(int))(StepArgs<T>) { return nullptr; }
-#define YCNR_X6D(NBV) \
-  template <>         \
-  void (*slab_x6d_kernel<float, NBV>(int k))(StepArgs<float>) { return k % 4 ? nullptr : k < 16 * NBV ? (pk3_k<NBV>(k) ? als_gram_slab_x6d_kernel<NBV, true, true> : als_gram_slab_x6d_kernel<NBV, true, false>) : als_gram_slab_x6d_kernel<NBV, false>; }
-YCNR_X6D(1) YCNR_X6D(2) YCNR_X6D(3) YCNR_X6D(4) YCNR_X6D(5) YCNR_X6D(6) YCNR_X6D(7) YCNR_X6D(8)
-#undef YCNR_X6D
+// The kernels of a half-step at k <= 128 and their dynamic LDS.  kernel_choice.h states which instantiations run.
+template <typename T>
+struct RowKernels {
+  void (*chunk)(StepArgs<T>), (*row)(StepArgs<T>), (*reduce)(StepArgs<T>);
+  void (*band)(StepArgs<T>, const T *const *, int32_t);
+  size_t ldsRow, ldsReduce;
+};
 
-// k = 16 (NB - 1) + 4 in float32 with the register solver: the instantiations that eliminate the four edge
-// columns first (SolveMfmaF32::solve_edge4)
-template <int NB, bool LDS_SOLVER>
-constexpr bool edge4_k(int k) { return YCNR_EDGE4_SOLVE && NB >= 2 && !LDS_SOLVER && k == 16 * (NB - 1) + 4; }
-
-template <typename T, int NB, bool LDS_SOLVER>
-void (*fused_x6d_kernel(int))(StepArgs<T>) { return nullptr; }
-#define YCNR_X6D(NBV, LDSV) \
-  template <>               \
-  void (*fused_x6d_kernel<float, NBV, LDSV>(int k))(StepArgs<float>) { return k % 4 ? nullptr : k < 16 * NBV ? (edge4_k<NBV, LDSV>(k) ? (pk3_k<NBV>(k) ? als_gram_solve_x6d_kernel<NBV, true, LDSV, true, true> : als_gram_solve_x6d_kernel<NBV, true, LDSV, true, false>) : (pk3_k<NBV>(k) ? als_gram_solve_x6d_kernel<NBV, true, LDSV, false, true> : als_gram_solve_x6d_kernel<NBV, true, LDSV, false, false>)) : als_gram_solve_x6d_kernel<NBV, false, LDSV, false>; }
-YCNR_X6D(1, false) YCNR_X6D(2, false) YCNR_X6D(3, false) YCNR_X6D(4, false) YCNR_X6D(5, false) YCNR_X6D(6, false) YCNR_X6D(7, false) YCNR_X6D(8, false)
-YCNR_X6D(1, true) YCNR_X6D(2, true) YCNR_X6D(3, true) YCNR_X6D(4, true) YCNR_X6D(5, true) YCNR_X6D(6, true) YCNR_X6D(7, true)
-#undef YCNR_X6D
-
-// the fused row kernel on the pre-split planes of the fixed matrix (GramX6P): k % 4 == 0, 16 (NB - 1) < k < 16 NB, register solver;
-// k = 16 (NB - 1) + 4: the last block packed into one slot, the four edge columns eliminated first
-template <typename T, int NB>
-void (*fused_x6p_kernel(int))(StepArgs<T>) { return nullptr; }
-#define YCNR_X6P(NBV) \
-  template <>         \
-  void (*fused_x6p_kernel<float, NBV>(int k))(StepArgs<float>) { return (k % 4 || k >= 16 * NBV || k <= 16 * (NBV - 1)) ? nullptr : (NBV >= 2 && planes_pack(k)) ? als_gram_solve_x6p_kernel<NBV, (NBV >= 2), (NBV >= 2)> : als_gram_solve_x6p_kernel<NBV, false, false>; }
-YCNR_X6P(1) YCNR_X6P(2) YCNR_X6P(3) YCNR_X6P(4) YCNR_X6P(5) YCNR_X6P(6) YCNR_X6P(7) YCNR_X6P(8)
-#undef YCNR_X6P
-
-// SLABX6: split chunks go through the bf16x6 Gramian kernel (plain slab layout), so the reduce
-// kernel reads plain slabs whatever form the fused kernel uses.
-template <typename T, int NB, bool LDS_SOLVER, bool EDGE, bool SLABX6>
-int launch_nbe(StepArgs<T> args, int64_t nUnits, int64_t nSplitUnits, int64_t nSplit, hipStream_t stream,
-               hipEvent_t *ev /* 5 events or null */, const DualPlan &dp) {
-  const size_t lds = SolverFor<T, NB, LDS_SOLVER>::type::lds_bytes();
-  void (*k0)(StepArgs<T>) = SLABX6 ? slab_x6_kernel<T, NB>() : als_gram_slab_kernel<T, NB, EDGE && !SLABX6>;
-  if (SLABX6 && slab_x6d_kernel<T, NB>(args.k) && !env_flags().noX6d) k0 = slab_x6d_kernel<T, NB>(args.k);
-  void (*k1)(StepArgs<T>) = als_gram_solve_kernel<T, NB, LDS_SOLVER, EDGE, false>;
-  void (*k2)(StepArgs<T>) = als_reduce_solve_kernel<T, NB, LDS_SOLVER, EDGE && !SLABX6, false>;
-  if constexpr (std::is_same<T, float>::value && !LDS_SOLVER)
-    if (dp.fewSlabs) k2 = als_reduce_solve_kernel<T, NB, LDS_SOLVER, EDGE && !SLABX6, false, true>;
-  if constexpr (std::is_same<T, float>::value && NB >= 2 && !LDS_SOLVER) {
-    if (edge4_k<NB, LDS_SOLVER>(args.k)) {
-      k1 = als_gram_solve_kernel<T, NB, LDS_SOLVER, EDGE, true>;
-      k2 = als_reduce_solve_kernel<T, NB, LDS_SOLVER, EDGE && !SLABX6, true>;
-      if (dp.fewSlabs) k2 = als_reduce_solve_kernel<T, NB, LDS_SOLVER, EDGE && !SLABX6, true, true>;
-    }
+// A choice to its instantiations.  Only forms that choose_kernels can return exist: the bf16x6 kernels are float32, the VALU
+// edge needs two blocks, the edge-first solve (E4) also the register solver, FEW float32 and the register solver, and there is
+// no x6d row kernel for eight blocks with the LDS solver.  A pointer stays null where the form does not exist.
+template <typename T, int NB, bool LDSV>
+void row_kernels_nb(const KernelChoice &c, RowKernels<T> &r) {
+  constexpr bool F32 = std::is_same<T, float>::value, EDGE = F32 && NB >= 2, E4 = EDGE && !LDSV;
+  using Fn = void (*)(StepArgs<T>);
+  r.ldsReduce = SolverFor<T, NB, LDSV>::type::lds_bytes();
+  r.ldsRow = c.rowLdsImage ? r.ldsReduce : 0;
+  if (c.chunk == kGramMfma) r.chunk = with_bool<EDGE>(c.chunkEdge, [](auto e) -> Fn { return als_gram_slab_kernel<T, NB, decltype(e)::value>; });
+  if (c.row == kGramMfma)
+    r.row = with_bool<EDGE>(c.rowEdge, [&](auto e) { return with_bool<E4>(c.rowE4, [](auto e4) -> Fn { return als_gram_solve_kernel<T, NB, LDSV, decltype(e)::value, decltype(e4)::value>; }); });
+  if constexpr (F32) {
+    if (c.chunk == kGramX6) r.chunk = als_gram_slab_x6_kernel<NB>;
+    if (c.chunk == kGramX6D)
+      r.chunk = !c.chunkPadRhs ? als_gram_slab_x6d_kernel<NB, false> : c.chunkPk3 ? als_gram_slab_x6d_kernel<NB, true, true> : als_gram_slab_x6d_kernel<NB, true, false>;
+    if constexpr (!(LDSV && NB == 8))
+      if (c.row == kGramX6D)
+        r.row = !c.rowPadRhs ? als_gram_solve_x6d_kernel<NB, false, LDSV, false> : with_bool<E4>(c.rowE4, [&](auto e4) -> Fn {
+          return c.rowPk3 ? als_gram_solve_x6d_kernel<NB, true, LDSV, decltype(e4)::value, true> : als_gram_solve_x6d_kernel<NB, true, LDSV, decltype(e4)::value, false>;
+        });
+    if constexpr (!LDSV)
+      if (c.row == kGramPlanes) r.row = with_bool<EDGE>(c.rowPack, [](auto p) -> Fn { return als_gram_solve_x6p_kernel<NB, decltype(p)::value, decltype(p)::value>; });
   }
-  if (SLABX6 && fused_x6d_kernel<T, NB, LDS_SOLVER>(args.k) && !env_flags().noX6d && !env_flags().noFusedX6d)
-    k1 = fused_x6d_kernel<T, NB, LDS_SOLVER>(args.k);
-  size_t ldsRow = lds;  // dynamic LDS of the row kernel: the solver's image
-  if constexpr (SLABX6 && !LDS_SOLVER && NB <= 8) {
-    if (args.planes && fused_x6p_kernel<T, NB>(args.k)) {  // the half-step split the fixed matrix into planes
-      k1 = fused_x6p_kernel<T, NB>(args.k);
-      ldsRow = 0;  // (its solver works in the slots of the Gramian)
-    }
-  }
-  const size_t pad = env_flags().k1LdsPad;  // experiments: limits blocks per CU
-  if (int rcl = set_max_lds(reinterpret_cast<const void *>(k1), ldsRow + pad)) return rcl;
-  if (int rcl = set_max_lds(reinterpret_cast<const void *>(k2), lds)) return rcl;
-  if (dp.only == 1) {
-    if (nSplitUnits > 0) {
-      hipLaunchKernelGGL(k0, dim3((unsigned)nSplitUnits), dim3(64), 0, stream, args);
-      HIP_TRY(hipGetLastError());
-    }
-    return YCNR_OK;
-  }
-  if (dp.only == 2) {
-    void (*kb)(StepArgs<T>, const T *const *, int32_t) = als_band_reduce_solve_kernel<T, NB, LDS_SOLVER, EDGE && !SLABX6, false>;
-    if constexpr (std::is_same<T, float>::value && NB >= 2 && !LDS_SOLVER)
-      if (edge4_k<NB, LDS_SOLVER>(args.k)) kb = als_band_reduce_solve_kernel<T, NB, LDS_SOLVER, EDGE && !SLABX6, true>;
-    if (int rcl = set_max_lds(reinterpret_cast<const void *>(kb), lds)) return rcl;
-    if (nSplit > 0) {
-      hipLaunchKernelGGL(kb, dim3((unsigned)nSplit), dim3(64), lds, stream, args, reinterpret_cast<const T *const *>(dp.bandSlab), (int32_t)dp.nBands);
-      HIP_TRY(hipGetLastError());
-    }
-    return YCNR_OK;
-  }
+  r.reduce = with_bool<EDGE>(c.reduceEdge, [&](auto e) { return with_bool<E4>(c.reduceE4, [&](auto e4) {
+    return with_bool<F32 && !LDSV>(c.reduceFew, [](auto few) -> Fn { return als_reduce_solve_kernel<T, NB, LDSV, decltype(e)::value, decltype(e4)::value, decltype(few)::value>; });
+  }); });
+  r.band = with_bool<EDGE>(c.reduceEdge, [&](auto e) { return with_bool<E4>(c.bandE4, [](auto e4) -> decltype(r.band) { return als_band_reduce_solve_kernel<T, NB, LDSV, decltype(e)::value, decltype(e4)::value>; }); });
+}
+
+// The kernels of this half-step: the choice from the arguments and the environment toggles, then the table
+template <typename T>
+int row_kernels(const StepArgs<T> &args, bool ldsSolver, bool edge, bool x6, bool fewSlabs, RowKernels<T> &r) {
+  const KernelChoice c = choose_kernels(std::is_same<T, double>::value, args.k, ldsSolver, edge, x6, args.planes != nullptr, fewSlabs,
+                                        env_flags().noX6d, env_flags().noFusedX6d, env_flags().noPk3);
+  r = RowKernels<T>{};
+  if (!dispatch_nb<1, 8>(c.nb, [&](auto nb) { ldsSolver ? row_kernels_nb<T, decltype(nb)::value, true>(c, r) : row_kernels_nb<T, decltype(nb)::value, false>(c, r); }))
+    return fail(YCNR_ERR_UNSUPPORTED, "factorsCount %d > %d is not supported by this build", args.k, kMaxFactors);
+  if (!r.chunk || !r.row || !r.reduce || !r.band) return fail(YCNR_ERR_UNSUPPORTED, "factorsCount %d: no kernel of the chosen form in this build", args.k);
+  return YCNR_OK;
+}
+
+// One half-step at k <= 128: [chunks of split rows -> slabs] [whole rows: Gramian + solve] [dual classes] [slabs -> solve]
+template <typename T>
+int launch_rows(const RowKernels<T> &rk, StepArgs<T> args, int64_t nUnits, int64_t nSplitUnits, int64_t nSplit, hipStream_t stream,
+                hipEvent_t *ev /* 5 events or null */, const DualPlan &dp) {
+  const size_t lds = rk.ldsReduce, ldsRow = rk.ldsRow + env_flags().k1LdsPad;  // (the pad: experiments, limits blocks per CU)
+  if (int rcl = set_max_lds(reinterpret_cast<const void *>(rk.row), ldsRow)) return rcl;
+  if (int rcl = set_max_lds(reinterpret_cast<const void *>(rk.reduce), lds)) return rcl;
   args.firstFused = (int32_t)nSplitUnits;
   if (ev) HIP_TRY(hipEventRecord(ev[0], stream));
   const bool branch = dp.slabStream != nullptr && nSplitUnits > 0;  // chunks -> reduce on their own branch
@@ -354,59 +331,35 @@ int launch_nbe(StepArgs<T> args, int64_t nUnits, int64_t nSplitUnits, int64_t nS
   if (branch || overlap) HIP_TRY(hipEventRecord(dp.fork, stream));
   if (branch) {
     HIP_TRY(hipStreamWaitEvent(dp.slabStream, dp.fork, 0));
-    hipLaunchKernelGGL(k0, dim3((unsigned)nSplitUnits), dim3(64), 0, dp.slabStream, args);
+    hipLaunchKernelGGL(rk.chunk, dim3((unsigned)nSplitUnits), dim3(64), 0, dp.slabStream, args);
     HIP_TRY(hipGetLastError());
     if (nSplit > 0) {
-      hipLaunchKernelGGL(k2, dim3((unsigned)nSplit), dim3(64), lds, dp.slabStream, args);
+      hipLaunchKernelGGL(rk.reduce, dim3((unsigned)nSplit), dim3(64), lds, dp.slabStream, args);
       HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipEventRecord(dp.slabJoin, dp.slabStream));
   } else if (nSplitUnits > 0) {
-    hipLaunchKernelGGL(k0, dim3((unsigned)nSplitUnits), dim3(64), 0, stream, args);
+    hipLaunchKernelGGL(rk.chunk, dim3((unsigned)nSplitUnits), dim3(64), 0, stream, args);
     HIP_TRY(hipGetLastError());
   }
   if (ev) HIP_TRY(hipEventRecord(ev[1], stream));
-  if (overlap) {  // dual classes first, on the side streams; then the row kernel on this one
-    for (int i = 0; i < dp.nSide; ++i) HIP_TRY(hipStreamWaitEvent(dp.side[i], dp.fork, 0));
-    dp.nextSide = 0;
-    int rc = launch_duals<T>(args, dp, stream);
-    if (rc) return rc;
-    for (int i = 0; i < dp.nSide; ++i) HIP_TRY(hipEventRecord(dp.join[i], dp.side[i]));
-  }
+  if (overlap)  // dual classes first, on the side streams; then the row kernel on this one
+    if (int rc = fork_duals<T>(args, dp, stream)) return rc;
   if (nPrimal > 0) {
-    hipLaunchKernelGGL(k1, dim3((unsigned)nPrimal), dim3(64), ldsRow + pad, stream, args);
+    hipLaunchKernelGGL(rk.row, dim3((unsigned)nPrimal), dim3(64), ldsRow, stream, args);
     HIP_TRY(hipGetLastError());
   }
   if (ev) HIP_TRY(hipEventRecord(ev[2], stream));
-  if (overlap) {
-    for (int i = 0; i < dp.nSide; ++i) HIP_TRY(hipStreamWaitEvent(stream, dp.join[i], 0));
-  } else if (dp.nPrimal >= 0) {
-    int rc = launch_duals<T>(args, dp, stream);
-    if (rc) return rc;
-  }
+  if (int rc = overlap ? join_duals(dp, stream) : dp.nPrimal >= 0 ? launch_duals<T>(args, dp, stream) : YCNR_OK) return rc;  // (or the classes here, in stream order)
   if (ev) HIP_TRY(hipEventRecord(ev[3], stream));
   if (branch) {
     HIP_TRY(hipStreamWaitEvent(stream, dp.slabJoin, 0));
   } else if (nSplit > 0) {
-    hipLaunchKernelGGL(k2, dim3((unsigned)nSplit), dim3(64), lds, stream, args);
+    hipLaunchKernelGGL(rk.reduce, dim3((unsigned)nSplit), dim3(64), lds, stream, args);
     HIP_TRY(hipGetLastError());
   }
   if (ev) HIP_TRY(hipEventRecord(ev[4], stream));
   return YCNR_OK;
-}
-
-// the VALU-edge Gramian exists for float32 and k = 16 (NB-1) + 4 only
-template <typename T, int NB, bool LDS_SOLVER>
-int launch_nb(const StepArgs<T> &args, int64_t nUnits, int64_t nSplitUnits, int64_t nSplit, hipStream_t stream, hipEvent_t *ev,
-              const DualPlan &dp, bool edge, bool x6) {
-  if constexpr (std::is_same<T, float>::value) {
-    if constexpr (NB >= 2) {
-      if (edge && x6) return launch_nbe<T, NB, LDS_SOLVER, true, true>(args, nUnits, nSplitUnits, nSplit, stream, ev, dp);
-      if (edge) return launch_nbe<T, NB, LDS_SOLVER, true, false>(args, nUnits, nSplitUnits, nSplit, stream, ev, dp);
-    }
-    if (x6) return launch_nbe<T, NB, LDS_SOLVER, false, true>(args, nUnits, nSplitUnits, nSplit, stream, ev, dp);
-  }
-  return launch_nbe<T, NB, LDS_SOLVER, false, false>(args, nUnits, nSplitUnits, nSplit, stream, ev, dp);
 }
 
 // k > 128 with k % 4 != 0: the kernels of that path need 16-byte rows, so the half-step runs on copies of
@@ -465,11 +418,7 @@ int launch_wg_nb(StepArgs<float> args, int64_t nSplitUnits, int64_t nPrimal, int
   const bool sideDuals = dp.nPrimal >= 0 && dp.nSide > 0 && dp.fork;
   if (sideDuals) {
     HIP_TRY(hipEventRecord(dp.fork, stream));
-    for (int i = 0; i < dp.nSide; ++i) HIP_TRY(hipStreamWaitEvent(dp.side[i], dp.fork, 0));
-    dp.nextSide = 0;
-    int rc = launch_duals<float>(args, dp, stream);
-    if (rc) return rc;
-    for (int i = 0; i < dp.nSide; ++i) HIP_TRY(hipEventRecord(dp.join[i], dp.side[i]));
+    if (int rc = fork_duals<float>(args, dp, stream)) return rc;
   }
   // NB = 16, YCNR_G32=1: the Gramians on 32 x 32 MFMAs, one wave per SIMD (als_gram32_kernels.hip.h) -- measured equal to
   // WgGram on one GPU's eighth of C5 (both are bound by the power the bf16 pipe + the split draw), so off
@@ -529,7 +478,7 @@ int launch_wg_nb(StepArgs<float> args, int64_t nSplitUnits, int64_t nPrimal, int
     if (rc) return rc;
   }
   if (sideDuals)
-    for (int i = 0; i < dp.nSide; ++i) HIP_TRY(hipStreamWaitEvent(stream, dp.join[i], 0));
+    if (int rc = join_duals(dp, stream)) return rc;
   if (ev) HIP_TRY(hipEventRecord(ev[3], stream));
   if (nSplit > 0) {
     hipLaunchKernelGGL(k2, dim3((unsigned)std::min(nSplit, cus)), dim3(kWgThreads), lds, stream, args, (int32_t)nSplit);
@@ -543,17 +492,10 @@ int launch_step_big(const StepArgs<float> &args, int64_t nUnits, int64_t nSplitU
                     hipEvent_t *ev, const DualPlan &dp, float *rowSlabs = nullptr, int64_t rowSlabRows = 0) {
   if (nUnits > 0x7fffffffLL) return fail(YCNR_ERR_UNSUPPORTED, "too many work units for one launch (%lld)", (long long)nUnits);
   const int64_t nPrimal = dp.nPrimal >= 0 ? dp.nPrimal : nUnits - nSplitUnits;
-  switch ((args.k + 15) / 16) {
-    case 9: return launch_wg_nb<9>(args, nSplitUnits, nPrimal, nSplit, stream, ev, dp, rowSlabs, rowSlabRows);
-    case 10: return launch_wg_nb<10>(args, nSplitUnits, nPrimal, nSplit, stream, ev, dp, rowSlabs, rowSlabRows);
-    case 11: return launch_wg_nb<11>(args, nSplitUnits, nPrimal, nSplit, stream, ev, dp, rowSlabs, rowSlabRows);
-    case 12: return launch_wg_nb<12>(args, nSplitUnits, nPrimal, nSplit, stream, ev, dp, rowSlabs, rowSlabRows);
-    case 13: return launch_wg_nb<13>(args, nSplitUnits, nPrimal, nSplit, stream, ev, dp, rowSlabs, rowSlabRows);
-    case 14: return launch_wg_nb<14>(args, nSplitUnits, nPrimal, nSplit, stream, ev, dp, rowSlabs, rowSlabRows);
-    case 15: return launch_wg_nb<15>(args, nSplitUnits, nPrimal, nSplit, stream, ev, dp, rowSlabs, rowSlabRows);
-    case 16: return launch_wg_nb<16>(args, nSplitUnits, nPrimal, nSplit, stream, ev, dp, rowSlabs, rowSlabRows);
-    default: return fail(YCNR_ERR_UNSUPPORTED, "factorsCount %d is outside the workgroup-per-row path", args.k);
-  }
+  int rc = YCNR_OK;
+  if (!dispatch_nb<9, 16>((args.k + 15) / 16, [&](auto nb) { rc = launch_wg_nb<decltype(nb)::value>(args, nSplitUnits, nPrimal, nSplit, stream, ev, dp, rowSlabs, rowSlabRows); }))
+    return fail(YCNR_ERR_UNSUPPORTED, "factorsCount %d is outside the workgroup-per-row path", args.k);
+  return rc;
 }
 
 // any factorsCount (als_gen_kernels.hip.h): batches of [Gramians -> slabs] [slabs -> solve], then the dual classes
@@ -658,28 +600,9 @@ int launch_step(const StepArgs<T> &args, int64_t nUnits, int64_t nSplitUnits, in
                 hipEvent_t *ev, bool ldsSolver = false, const DualPlan &dp = DualPlan(), bool edge = false, bool x6 = false) {
   if (nUnits > 0x7fffffffLL || nSplit > 0x7fffffffLL)
     return fail(YCNR_ERR_UNSUPPORTED, "too many work units for one launch (%lld)", (long long)nUnits);
-  const int nb = (args.k + 15) / 16;
-  switch (nb) {
-    case 1: return ldsSolver ? launch_nb<T, 1, true>(args, nUnits, nSplitUnits, nSplit, stream, ev, dp, edge, x6)
-                             : launch_nb<T, 1, false>(args, nUnits, nSplitUnits, nSplit, stream, ev, dp, edge, x6);
-    case 2: return ldsSolver ? launch_nb<T, 2, true>(args, nUnits, nSplitUnits, nSplit, stream, ev, dp, edge, x6)
-                             : launch_nb<T, 2, false>(args, nUnits, nSplitUnits, nSplit, stream, ev, dp, edge, x6);
-    case 3: return ldsSolver ? launch_nb<T, 3, true>(args, nUnits, nSplitUnits, nSplit, stream, ev, dp, edge, x6)
-                             : launch_nb<T, 3, false>(args, nUnits, nSplitUnits, nSplit, stream, ev, dp, edge, x6);
-    case 4: return ldsSolver ? launch_nb<T, 4, true>(args, nUnits, nSplitUnits, nSplit, stream, ev, dp, edge, x6)
-                             : launch_nb<T, 4, false>(args, nUnits, nSplitUnits, nSplit, stream, ev, dp, edge, x6);
-    case 5: return ldsSolver ? launch_nb<T, 5, true>(args, nUnits, nSplitUnits, nSplit, stream, ev, dp, edge, x6)
-                             : launch_nb<T, 5, false>(args, nUnits, nSplitUnits, nSplit, stream, ev, dp, edge, x6);
-    case 6: return ldsSolver ? launch_nb<T, 6, true>(args, nUnits, nSplitUnits, nSplit, stream, ev, dp, edge, x6)
-                             : launch_nb<T, 6, false>(args, nUnits, nSplitUnits, nSplit, stream, ev, dp, edge, x6);
-    case 7: return ldsSolver ? launch_nb<T, 7, true>(args, nUnits, nSplitUnits, nSplit, stream, ev, dp, edge, x6)
-                             : launch_nb<T, 7, false>(args, nUnits, nSplitUnits, nSplit, stream, ev, dp, edge, x6);
-    case 8: return ldsSolver ? launch_nb<T, 8, true>(args, nUnits, nSplitUnits, nSplit, stream, ev, dp, edge, x6)
-                             : launch_nb<T, 8, false>(args, nUnits, nSplitUnits, nSplit, stream, ev, dp, edge, x6);
-    default:
-      return fail(YCNR_ERR_UNSUPPORTED, "factorsCount %d > %d is not supported by this build", args.k,
-                  kMaxFactors);
-  }
+  RowKernels<T> rk;
+  if (int rc = row_kernels<T>(args, ldsSolver, edge, x6, dp.fewSlabs, rk)) return rc;
+  return launch_rows<T>(rk, args, nUnits, nSplitUnits, nSplit, stream, ev, dp);
 }
 
 int slab_nb(int k) { return (k + 15) / 16; }
@@ -973,6 +896,15 @@ struct ycnr_als {
   int64_t rows(int side) const { return side == YCNR_BY_USER ? opt.totalUsersCount : opt.totalItemsCount; }
   size_t ts() const { return tsize(opt.dtype); }
 };
+
+// the kernels' arguments for one piece of a side: its schedule and ratings, the two factor matrices (or their padded copies)
+template <typename T>
+static StepArgs<T> step_args(const ycnr_als *h, int side, const Part &part, const void *fixed, void *solved) {
+  const double lambda = side == YCNR_BY_USER ? h->copt.userFactReg : h->copt.itemFactReg;
+  return StepArgs<T>{part.S.dUnits, part.S.dSplit, part.R.dIndx, (const T *)part.R.dVals, (const T *)fixed, (const T *)h->dZeros, (T *)solved,
+                     (T *)part.S.dSlabs, h->dErr, lambda, h->copt.factorsCount, 0, 0,
+                     use_slab_x6(h->copt, side) ? (uint32_t)(h->rows(1 - side) * h->copt.factorsCount * 4) : 0u};
+}
 
 extern "C" {
 
@@ -1972,14 +1904,10 @@ static int launch_part(ycnr_als *h, int side, Part &part, hipStream_t stream, bo
   const Ratings &R = part.R;
   const Schedule &S = part.S;
   hipEvent_t *ev = branches ? nullptr : part.ev;
-  const double lambda = side == YCNR_BY_USER ? h->copt.userFactReg : h->copt.itemFactReg;
   if (h->copt.dtype == YCNR_F32) {
-    const int kk = h->copt.factorsCount;  // (= kPad when the matrices are padded)
-    const float *fixedM = h->kPad ? h->padded[1 - side] : (const float *)h->factors[1 - side];
-    float *solvedM = h->kPad ? h->padded[side] : (float *)h->factors[side];
-    StepArgs<float> a{S.dUnits, S.dSplit, R.dIndx, (const float *)R.dVals, fixedM,
-                      (const float *)h->dZeros, solvedM, (float *)S.dSlabs, h->dErr, lambda, kk, 0, 0,
-                      use_slab_x6(h->copt, side) ? (uint32_t)(h->rows(1 - side) * h->copt.factorsCount * 4) : 0u};
+    // (copt.factorsCount = kPad when the matrices are padded)
+    StepArgs<float> a = h->kPad ? step_args<float>(h, side, part, h->padded[1 - side], h->padded[side])
+                                : step_args<float>(h, side, part, h->factors[1 - side], h->factors[side]);
     if (h->kPad) a.kReal = h->opt.factorsCount;
     if (h->planes[1 - side] && h->planesValid[1 - side] && use_planes(h->copt, side)) {
       a.planes = h->planes[1 - side];
@@ -2026,8 +1954,7 @@ static int launch_part(ycnr_als *h, int side, Part &part, hipStream_t stream, bo
     }
     return YCNR_OK;
   }
-  StepArgs<double> a{S.dUnits, S.dSplit, R.dIndx, (const double *)R.dVals, (const double *)h->factors[1 - side],
-                     (const double *)h->dZeros, (double *)h->factors[side], (double *)S.dSlabs, h->dErr, lambda, h->copt.factorsCount, 0, 0, 0u};
+  const StepArgs<double> a = step_args<double>(h, side, part, h->factors[1 - side], h->factors[side]);
   if (is_gen(YCNR_F64, h->copt.factorsCount)) return launch_step_gen<double>(a, S.genBatches, stream, ev, DualPlan());
   DualPlan dpd;  // float64 has no dual classes; the chunk branch of the small-upload form applies
   dpd.fork = part.fork;
@@ -2103,7 +2030,6 @@ static int step_banded_t(ycnr_als *h, int side) {
   if (comm && (c.world != B.world || c.rank != B.rank)) return fail(YCNR_ERR_STATE, "step: the banded upload of this side was made for another communicator");
   hipStream_t stream = h->stream;
   const size_t ts = sizeof(T), slabBytes = (size_t)B.slabElems * ts;
-  const double lambda = side == YCNR_BY_USER ? h->copt.userFactReg : h->copt.itemFactReg;
   if (comm && c.transport == YCNR_COMM_IPC) {
     if (c.pendingFinish) {  // (as ycnr_als_step_async: a half-step the peers were still pushing must be complete first)
       HIP_TRY(hipStreamSynchronize(stream));
@@ -2111,12 +2037,11 @@ static int step_banded_t(ycnr_als *h, int side) {
     }
     if (int rcb = ipc_enter(c)) return rcb;
   }
-  StepArgs<T> a{S.dUnits, S.dSplit, part.R.dIndx, (const T *)part.R.dVals, (const T *)h->factors[1 - side], (const T *)h->dZeros, (T *)h->factors[side],
-                (T *)S.dSlabs, h->dErr, lambda, h->copt.factorsCount, 0, 0,
-                use_slab_x6(h->copt, side) ? (uint32_t)(h->rows(1 - side) * h->copt.factorsCount * 4) : 0u};
-  DualPlan dp;
-  dp.noX6 = (h->copt.flags & YCNR_FLAG_NO_BF16X6) != 0;
-  const bool lds = (h->copt.flags & YCNR_FLAG_LDS_SOLVER) != 0, edge = use_valu_edge(h->copt), x6 = use_slab_x6(h->copt, side);
+  const StepArgs<T> a = step_args<T>(h, side, part, h->factors[1 - side], h->factors[side]);
+  // the chunk kernel and the band reduce of this k (no row kernel, no dual classes)
+  RowKernels<T> rk;
+  if (int rc = row_kernels<T>(a, (h->copt.flags & YCNR_FLAG_LDS_SOLVER) != 0, use_valu_edge(h->copt), use_slab_x6(h->copt, side), false, rk)) return rc;
+  if (int rc = set_max_lds(reinterpret_cast<const void *>(rk.band), rk.ldsReduce)) return rc;
   HIP_TRY(hipEventRecord(part.ev[0], stream));
   const int bpr = (int)(B.rankBands[(size_t)B.rank + 1] - B.rankBands[(size_t)B.rank]);
   // The groups are dealt over up to four streams (the handle's two piece streams and two of its side streams): a group is an
@@ -2155,12 +2080,12 @@ static int step_banded_t(ycnr_als *h, int side) {
         nu += B.groupUnits[(size_t)((B.rank + t) % B.world)];
         ns += B.groupSums[(size_t)((B.rank + t) % B.world)];
       }
+      if (nu > 0x7fffffffLL) return fail(YCNR_ERR_UNSUPPORTED, "too many work units for one launch (%lld)", (long long)nu);
       if (nu > 0) {
         StepArgs<T> ag = a;
         ag.units = S.dUnits + B.groupUnit0[(size_t)g0];
-        dp.only = 1;
-        int rc = launch_step<T>(ag, nu, nu, 0, ps, nullptr, lds, dp, edge, x6);
-        if (rc) return rc;
+        hipLaunchKernelGGL(rk.chunk, dim3((unsigned)nu), dim3(64), 0, ps, ag);
+        HIP_TRY(hipGetLastError());
       }
       if (ns > 0) {
         hipLaunchKernelGGL(als_slab_sum_kernel<T>, dim3((unsigned)ns), dim3(256), 0, ps, (T *)S.dSlabs, (const SlabSum *)B.dSums + B.groupSum0[(size_t)g0], B.slabElems);
@@ -2211,12 +2136,10 @@ static int step_banded_t(ycnr_als *h, int side) {
     HIP_TRY(hipStreamSynchronize(c.stream));  // this rank's pushes have landed ...
     if (int rcb = shm_barrier(c)) return rcb;  // ... and everybody's
   }
+  if (S.nSplit > 0x7fffffffLL) return fail(YCNR_ERR_UNSUPPORTED, "too many split rows for one launch (%lld)", (long long)S.nSplit);
   if (S.nSplit > 0) {
-    dp.only = 2;
-    dp.bandSlab = B.dTable;
-    dp.nBands = B.nBands;
-    int rc = launch_step<T>(a, 0, 0, S.nSplit, stream, nullptr, lds, dp, edge, x6);
-    if (rc) return rc;
+    hipLaunchKernelGGL(rk.band, dim3((unsigned)S.nSplit), dim3(64), rk.ldsReduce, stream, a, reinterpret_cast<const T *const *>(B.dTable), (int32_t)B.nBands);
+    HIP_TRY(hipGetLastError());
   }
   HIP_TRY(hipEventRecord(part.ev[4], stream));
   h->exchangedInStep = comm;
