@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define YCNR_ALS_ABI_VERSION 4 /* 4: + ycnr_als_comm_info, ycnr_als_last_rmse_ms (nothing changed or removed); later, still 4: + ycnr_als_recommend */
+#define YCNR_ALS_ABI_VERSION 4 /* 4: + ycnr_als_comm_info, ycnr_als_last_rmse_ms (nothing changed or removed); later, still 4: + ycnr_als_recommend, + ycnr_als_fold_in, ycnr_als_recommend_for_ratings */
 
 /* error codes */
 #define YCNR_OK 0
@@ -444,6 +444,50 @@ int ycnr_recommend_items(int dtype, int32_t k, int64_t nUsers, const void *userR
 int ycnr_als_recommend(ycnr_als *h, int64_t nUsers, const int32_t *userIds, const int64_t *skipPtr, const int32_t *skipIds,
                        double globalAvgShift, double minRecommendRating, int32_t limit, int32_t *outIds, double *outPredict,
                        int32_t *outCount, double *deviceMs);
+
+/* ---- Fold-in: rows solved from ratings given in the call ----------------------------------------
+ *
+ * The reference gives up on a user without a trained row (the else branch of YcnrController.recommendItemsForUser,
+ * lib/YcnrController.js:275-280: "User hasn't list yet ... We can't give him personal recommendations"), and its warm start
+ * (EmfMaster.js:347-358) gives new users and items random rows, which recommend noise until a full retrain.  With ALS a new
+ * row is one regularised least-squares solve against the fixed opposite matrix, x = (Y^T Y + lambda n I)^-1 Y^T r -- what
+ * one row of a half-step computes (EmfWorker.mw_calcTrainAlsPortion, lib/emf/EmfWorker.js:214-248) -- and everything it needs
+ * is on the handle.
+ *
+ * ycnr_als_fold_in
+ *   side       YCNR_BY_USER: the rows are new users, indx are item ids, the fixed matrix is the handle's item matrix;
+ *              YCNR_BY_ITEM: the mirror case (a new item)
+ *   rowPtr     int64[nRows + 1] offsets relative to the request (rowPtr[0] == 0), host array like indx / vals;
+ *              vals in the handle's dtype
+ *   lambda     the side's userFactReg / itemFactReg of the handle's options (what ycnr_als_step uses)
+ *   outRows    nRows x factorsCount in the handle's dtype
+ *   outStatus  per row: 0 solved; 1 the normal matrix had a pivot p with !(p > 0) (NaN / Inf input): the row is all zeros;
+ *              2 the row has no ratings: all zeros, nothing solved.  A non-zero status is NOT an error return.
+ *   storeIds   (may be NULL) row r with status 0 is also written into the handle's own matrix of `side` at row storeIds[r]
+ *              (this rank's replica only; nothing is exchanged); rows with another status leave the matrix untouched.
+ *              This makes a folded-in item recommendable and a folded-in user reachable by ycnr_als_recommend.
+ * factorsCount <= 128: one kernel (csrc/foldin_kernels.hip.h), one workgroup per row, ALL arithmetic in float64 whatever the
+ * handle's dtype -- a float32 handle's row is the float64 solution of its float32 inputs, rounded once -- and every sum in an
+ * order fixed by the row alone: a row's bits do not depend on what else the request holds.  Beyond 128 the request runs
+ * through the kernels of a half-step, out of place, in the handle's precision; those name only one failing row, so there a
+ * failure marks EVERY solved row of the call with status 1 (zeros, nothing stored).
+ * YCNR_ERR_INVALID (outputs and matrices untouched): null pointers, rowPtr[0] != 0 or decreasing, a column id outside the
+ * fixed side, a store id outside the side or repeated.  nRows == 0 is YCNR_OK.
+ * Enqueued on the handle's stream behind the half-steps in flight (like ycnr_als_rmse), returns with the results on the
+ * host; the device buffers stay with the handle (a second call of the same size allocates nothing).  LOCAL, not collective.
+ * deviceMs (may be NULL): the kernels, between two HIP events.
+ *
+ * ycnr_als_recommend_for_ratings: fold-in of the user side into a buffer of the handle, then the top-N kernels of
+ * ycnr_als_recommend on that buffer, with no host round trip in between.  ratPtr / ratIds / ratVals: the request's ratings
+ * (as rowPtr / indx / vals above); skip lists, limit, threshold, fused / score-matrix choice and output layout exactly as
+ * ycnr_als_recommend.  outRows (may be NULL): the solved rows, the bits ycnr_als_fold_in returns; outStatus as above; users
+ * with a non-zero status get outCount = 0. */
+int ycnr_als_fold_in(ycnr_als *h, int side, int64_t nRows, const int64_t *rowPtr, const int32_t *indx, const void *vals,
+                     const int32_t *storeIds /* may be NULL */, void *outRows, int32_t *outStatus, double *deviceMs);
+int ycnr_als_recommend_for_ratings(ycnr_als *h, int64_t nUsers, const int64_t *ratPtr, const int32_t *ratIds, const void *ratVals,
+                                   const int64_t *skipPtr, const int32_t *skipIds, double globalAvgShift, double minRecommendRating,
+                                   int32_t limit, int32_t *outIds, double *outPredict, int32_t *outCount, void *outRows /* may be NULL */,
+                                   int32_t *outStatus, double *deviceMs);
 
 #ifdef __cplusplus
 }

@@ -120,6 +120,63 @@ def main():
             n1 += ycnr_als.als_calc_portion(0.05, kf, rows_, indx_, vals_, Vf, Uf0)
         dt1 = time.perf_counter() - t0p
         level1[name] = {"portions_per_s": round(len(portions) / dt1, 1), "ratings_per_s": round(n1 / dt1), "ms_per_portion": round(dt1 / len(portions) * 1e3, 3)}
+    # Fold-in: the 2048 request users carry the rating lists of the synthetic users above and have NO row on the handle.
+    # Yardstick, in this run: the level-1 route a caller has today -- the item matrix pinned once (outside the timing, still
+    # pinned from the loop above), ycnr_sAlsCalcPortion on the same rows, ycnr_recommend_items on the result -- against
+    # ycnr_als_recommend_for_ratings on a handle that holds the item matrix.  Each path on its second call.
+    f_ptr, f_idx, f_val = sp, np.ascontiguousarray(sk, np.int32), np.ascontiguousarray(vals_u[:int(rp_u[nrec])], np.float32)
+    f_portion = csr_to_portion(a_np, 0, nrec)
+
+    def yardstick(portion, ptr, skip, n):
+        ux = np.zeros((n, kf), np.float32)
+        ycnr_als.als_calc_portion(0.05, kf, *portion, Vf, ux)
+        return ycnr_als.recommend_items(ux, Vf, ptr, skip, 6.4, 7.0, 20)
+
+    fdev = ycnr_als.AlsDevice(kf, nrec, by_user.cols)
+    fdev.set_factors("byItem", Vf)
+    yardstick(f_portion, sp, sk, nrec)
+    t0w = time.perf_counter()
+    y_ids, y_pred, y_cnt, y_ms = yardstick(f_portion, sp, sk, nrec)
+    wall_yard = (time.perf_counter() - t0w) * 1e3
+    fdev.recommend_for_ratings(f_ptr, f_idx, f_val, sp, sk, 6.4, 7.0, 20)
+    t0w = time.perf_counter()
+    f_ids, f_pred, f_cnt, f_rows, f_status, f_ms = fdev.recommend_for_ratings(f_ptr, f_idx, f_val, sp, sk, 6.4, 7.0, 20)
+    wall_fold = (time.perf_counter() - t0w) * 1e3
+    _, _, ms_fold_only = fdev.fold_in("byUser", f_ptr, f_idx, f_val)
+    assert (f_status == np.where(np.diff(f_ptr) > 0, 0, 2)).all()
+    # (the yardstick solves in float32, the fold-in in float64: the lists agree except where two predicts are a rounding apart)
+    same_first = float(np.mean(f_ids[:, 0] == y_ids[:, 0]))
+    u1 = 5
+    one_ptr = np.array([0, sp[u1 + 1] - sp[u1]], np.int64)
+    one_idx, one_val = f_idx[sp[u1]:sp[u1 + 1]], f_val[sp[u1]:sp[u1 + 1]]
+    one_portion = (np.array([1, 0, len(one_idx)], np.int32), one_idx, one_val)
+    wall_one_y, wall_one_f = [], []
+    yardstick(one_portion, one_ptr, one_idx, 1)
+    fdev.recommend_for_ratings(one_ptr, one_idx, one_val, one_ptr, one_idx, 6.4, 7.0, 20)
+    for _ in range(20):  # the two paths interleaved
+        t0w = time.perf_counter()
+        yardstick(one_portion, one_ptr, one_idx, 1)
+        wall_one_y.append((time.perf_counter() - t0w) * 1e3)
+        t0w = time.perf_counter()
+        fdev.recommend_for_ratings(one_ptr, one_idx, one_val, one_ptr, one_idx, 6.4, 7.0, 20)
+        wall_one_f.append((time.perf_counter() - t0w) * 1e3)
+    fdev.destroy()
+    # floor COMPUTED from peak rates (not measured): the Gramian's float64 MFMAs (28 upper tiles of 16 x 16 at k = 100, 2048 flops per
+    # 16x16x4 MFMA, ratings padded to panels of 16) at the 78.6 Tflop/s of the float64 matrix cores, plus k^3 / 3 float64 flops of
+    # the factorisation per row at the same vector rate
+    f_cnts = np.diff(f_ptr)
+    gram_flops = float((((f_cnts + 15) // 16) * 4 * 28 * 2048).sum())
+    solve_flops = float(nrec) * kf ** 3 / 3
+    fold_in = {"users": nrec, "items": int(by_user.cols), "factorsCount": kf, "limit": 20, "ratings": int(f_ptr[-1]),
+               "resident": {"kernel_ms": round(f_ms, 3), "fold_in_kernel_ms": round(ms_fold_only, 3), "wall_ms": round(wall_fold, 3),
+                            "wall_ms_one_user": round(float(np.median(wall_one_f)), 4)},
+               "level1_route": {"recommend_kernel_ms": round(y_ms, 3), "wall_ms": round(wall_yard, 3),
+                                "wall_ms_one_user": round(float(np.median(wall_one_y)), 4),
+                                "note": "item matrix pinned outside the timing; the portion op reports no device time of its own"},
+               "speedup_wall": round(wall_yard / wall_fold, 2),
+               "speedup_wall_one_user": round(float(np.median(wall_one_y)) / float(np.median(wall_one_f)), 2),
+               "same_first_item_fraction": round(same_first, 4), "mean_recommended": float(f_cnt.mean()),
+               "computed_floor_ms": round((gram_flops + solve_flops) / 78.6e12 * 1e3, 4)}
     ycnr_als.release_portion_state()
     level1["portion"] = "10 000 ratings of consecutive users (byUser step), k = 100, float32, host buffers in and out"
     # algorithmic bytes: the split reads and writes one byte per rating (+ row pointers); the
@@ -164,6 +221,7 @@ def main():
                                "speedup_kernel": round(ms_rec / ms_res, 2), "speedup_wall": round(wall_rec / wall_res, 2),
                                "checked": "ids, predicts and counts equal to the one-shot entry's, bit for bit"},
         "level1_portion_op": level1,
+        "fold_in": fold_in,
         "sets": {"train": int(tot[1]), "validate": int(tot[2]), "test": int(tot[3])},
         "maxRatingsPerUser": int(cnt_u.max()), "maxRatingsPerItem": int(cnt_i.max()),
         "totalRatingsAvg": float(sum_u.sum() / cnt_u.sum()),

@@ -645,6 +645,69 @@ napi_value Recommend(napi_env env, napi_callback_info info) {
   return num(env, ms);
 }
 
+// foldIn(handle, side, rowPtr, indx: Int32Array, vals, storeIds: Int32Array | null, outRows, outStatus: Int32Array(nRows)) -> kernel ms
+// (ycnr_als_fold_in: rows solved from the ratings given here against the opposite matrix the handle holds; vals / outRows in the handle's dtype)
+napi_value FoldIn(napi_env env, napi_callback_info info) {
+  size_t argc = 8;
+  napi_value a[8];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, a, nullptr, nullptr));
+  Handle *hd = argc >= 8 ? handle_of(env, a[0]) : nullptr;
+  if (!hd) return throw_msg(env, "foldIn(handle, side, rowPtr, indx, vals, storeIds, outRows, outStatus)");
+  View rp = view_of(env, a[2]), ix = view_of(env, a[3]), va = view_of(env, a[4]), orow = view_of(env, a[6]), ost = view_of(env, a[7]);
+  napi_valuetype st;
+  napi_typeof(env, a[5], &st);
+  const bool store = st != napi_undefined && st != napi_null;
+  View sv = store ? view_of(env, a[5]) : View();
+  int64_t side;
+  std::vector<int64_t> rowPtr;
+  const napi_typedarray_type want = hd->dtype == YCNR_F64 ? napi_float64_array : napi_float32_array;
+  if (!rp.ok || !ix.ok || !va.ok || !orow.ok || !ost.ok || (store && (!sv.ok || sv.type != napi_int32_array)) || !get_int(env, a[1], &side) ||
+      !to_i64(rp, rowPtr) || rowPtr.empty() || ix.type != napi_int32_array || va.type != want || orow.type != want || ost.type != napi_int32_array)
+    return throw_msg(env, "invalid type!");  // cpp_utils/cpp_utils.js:12
+  const size_t nRows = rowPtr.size() - 1;
+  if (rowPtr.back() < 0 || (size_t)rowPtr.back() > ix.length || (size_t)rowPtr.back() > va.length || orow.length < nRows * (size_t)hd->k ||
+      ost.length < nRows || (store && sv.length < nRows))
+    return throw_msg(env, "array lengths do not match");
+  double ms = 0;
+  int rc = ycnr_als_fold_in(hd->h, (int)side, (int64_t)nRows, rowPtr.data(), static_cast<const int32_t *>(ix.data), va.data,
+                            store ? static_cast<const int32_t *>(sv.data) : nullptr, orow.data, static_cast<int32_t *>(ost.data), &ms);
+  if (rc) return throw_last(env, "foldIn", rc);
+  return num(env, ms);
+}
+
+// recommendForRatings(handle, ratPtr, ratIds: Int32Array, ratVals, skipPtr, skipIds: Int32Array, globalAvgShift, minRecommendRating, limit,
+//                     outIds, outPredict, outCount, outRows, outStatus) -> kernel ms   (ycnr_als_recommend_for_ratings)
+napi_value RecommendForRatings(napi_env env, napi_callback_info info) {
+  size_t argc = 14;
+  napi_value a[14];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, a, nullptr, nullptr));
+  Handle *hd = argc >= 14 ? handle_of(env, a[0]) : nullptr;
+  if (!hd)
+    return throw_msg(env, "recommendForRatings(handle, ratPtr, ratIds, ratVals, skipPtr, skipIds, shift, minRating, limit, outIds, outPredict, outCount, outRows, outStatus)");
+  View rp = view_of(env, a[1]), ri = view_of(env, a[2]), rv = view_of(env, a[3]), sp = view_of(env, a[4]), sk = view_of(env, a[5]), oi = view_of(env, a[9]),
+       op = view_of(env, a[10]), oc = view_of(env, a[11]), orow = view_of(env, a[12]), ost = view_of(env, a[13]);
+  int64_t limit;
+  double shift, minRating;
+  std::vector<int64_t> ratPtr, skipPtr;
+  const napi_typedarray_type want = hd->dtype == YCNR_F64 ? napi_float64_array : napi_float32_array;
+  if (!rp.ok || !ri.ok || !rv.ok || !sp.ok || !sk.ok || !oi.ok || !op.ok || !oc.ok || !orow.ok || !ost.ok || !get_double(env, a[6], &shift) ||
+      !get_double(env, a[7], &minRating) || !get_int(env, a[8], &limit) || !to_i64(rp, ratPtr) || !to_i64(sp, skipPtr) || ratPtr.empty() ||
+      ri.type != napi_int32_array || rv.type != want || sk.type != napi_int32_array || oi.type != napi_int32_array || op.type != napi_float64_array ||
+      oc.type != napi_int32_array || orow.type != want || ost.type != napi_int32_array)
+    return throw_msg(env, "invalid type!");  // cpp_utils/cpp_utils.js:12
+  const size_t nUsers = ratPtr.size() - 1;
+  if (limit < 1 || skipPtr.size() != nUsers + 1 || skipPtr.back() < 0 || (size_t)skipPtr.back() > sk.length || ratPtr.back() < 0 ||
+      (size_t)ratPtr.back() > ri.length || (size_t)ratPtr.back() > rv.length || oi.length < nUsers * (size_t)limit || op.length < nUsers * (size_t)limit ||
+      oc.length < nUsers || orow.length < nUsers * (size_t)hd->k || ost.length < nUsers)
+    return throw_msg(env, "array lengths do not match");
+  double ms = 0;
+  int rc = ycnr_als_recommend_for_ratings(hd->h, (int64_t)nUsers, ratPtr.data(), static_cast<const int32_t *>(ri.data), rv.data, skipPtr.data(),
+                                          static_cast<const int32_t *>(sk.data), shift, minRating, (int32_t)limit, static_cast<int32_t *>(oi.data),
+                                          static_cast<double *>(op.data), static_cast<int32_t *>(oc.data), orow.data, static_cast<int32_t *>(ost.data), &ms);
+  if (rc) return throw_last(env, "recommendForRatings", rc);
+  return num(env, ms);
+}
+
 // N2: csrFromTriplets(rowIdx: Int32Array, colIdx: Int32Array, vals, rows, cols, rowPtr: Float64Array(rows+1) out,
 //                     indx: Int32Array(n) out, outVals out) -> kernel ms
 napi_value CsrFromTriplets(napi_env env, napi_callback_info info) {
@@ -768,6 +831,8 @@ napi_value Init(napi_env env, napi_value exports) {
       {"step", nullptr, Step, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"rmse", nullptr, Rmse, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"recommend", nullptr, Recommend, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+      {"foldIn", nullptr, FoldIn, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+      {"recommendForRatings", nullptr, RecommendForRatings, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"splitToSets", nullptr, SplitToSets, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"ratingStats", nullptr, RatingStats, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"csrFromTriplets", nullptr, CsrFromTriplets, nullptr, nullptr, nullptr, napi_enumerable, nullptr},

@@ -16,6 +16,7 @@
 #include "prep_kernels.hip.h"
 #include <hipcub/hipcub.hpp>
 #include "recommend_kernels.hip.h"
+#include "foldin_kernels.hip.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -870,9 +871,13 @@ struct ycnr_als {
     void *p = nullptr;
     size_t cap = 0;
   };
-  enum { REC_USER_IDS, REC_SKIP_PTR, REC_SKIP, REC_PART_V, REC_PART_I, REC_IDS, REC_PRED, REC_CNT, REC_ROWS, REC_SCORES, REC_NBUF };
+  enum { REC_USER_IDS, REC_SKIP_PTR, REC_SKIP, REC_PART_V, REC_PART_I, REC_IDS, REC_PRED, REC_CNT, REC_ROWS, REC_SCORES,
+         // ycnr_als_fold_in / ycnr_als_recommend_for_ratings: the request's CSR, the solved rows and their status, the ids to store at;
+         // factorsCount > 128: the plan of the step kernels (units, split rows, slabs) and their error record
+         FOLD_PTR, FOLD_INDX, FOLD_VALS, FOLD_ROWS, FOLD_STATUS, FOLD_STORE, FOLD_UNITS, FOLD_SPLIT, FOLD_SLABS, FOLD_ERR, FOLD_PAD, REC_NBUF };
   RecBuf rec[REC_NBUF];
   hipEvent_t recEv[2] = {nullptr, nullptr};
+  PiecePlan foldPlan;  // ycnr_als_fold_in beyond 128 factors: the plan whose lists are being copied to the device
   ErrInfo *dErr = nullptr;
   // The error record is never reset on the device: its count only grows, the host remembers what it has seen
   // (errSeen) and gets the record through an 8-byte copy into page-locked memory at the end of every half-step
@@ -2515,9 +2520,9 @@ constexpr int64_t kRecFusedBatch = 65536;  // users per launch of the fused kern
 
 // one batch of the fused path: scores + per-workgroup lists, then the merge into the output layout
 template <typename T>
-void launch_topn(ycnr_als *h, int64_t u0, int64_t nb, unsigned yblk, size_t lds, double shift, double thr, int take, int limit) {
+void launch_topn(ycnr_als *h, const void *users, int64_t u0, int64_t nb, unsigned yblk, size_t lds, double shift, double thr, int take, int limit) {
   const unsigned ublk = (unsigned)((nb + 15) / 16);
-  hipLaunchKernelGGL(recommend_topn_kernel<T>, dim3(ublk, yblk), dim3(256), lds, h->stream, (const T *)h->factors[YCNR_BY_USER],
+  hipLaunchKernelGGL(recommend_topn_kernel<T>, dim3(ublk, yblk), dim3(256), lds, h->stream, (const T *)users,
                      (const int32_t *)h->rec[ycnr_als::REC_USER_IDS].p + u0, nb, (const T *)h->factors[YCNR_BY_ITEM], h->opt.totalItemsCount,
                      (int)h->opt.factorsCount, shift, thr, (const int64_t *)h->rec[ycnr_als::REC_SKIP_PTR].p + u0,
                      (const int32_t *)h->rec[ycnr_als::REC_SKIP].p, take, (double *)h->rec[ycnr_als::REC_PART_V].p,
@@ -2529,14 +2534,14 @@ void launch_topn(ycnr_als *h, int64_t u0, int64_t nb, unsigned yblk, size_t lds,
 
 // one batch of the score-matrix path: the kernels of ycnr_recommend_items on the gathered user rows
 template <typename T>
-void launch_scores_select(ycnr_als *h, int64_t u0, int64_t nb, bool valu, bool anySkip, double shift, double minRating, int take, int limit) {
+void launch_scores_select(ycnr_als *h, const void *users, int64_t u0, int64_t nb, bool valu, bool anySkip, double shift, double minRating, int take, int limit) {
   const int k = h->opt.factorsCount;
   const int64_t totalItems = h->opt.totalItemsCount;
   const size_t kp = (size_t)((k + 15) & ~15);
   T *rows = (T *)h->rec[ycnr_als::REC_ROWS].p;
   double *scores = (double *)h->rec[ycnr_als::REC_SCORES].p;
   const int64_t *skipPtr = (const int64_t *)h->rec[ycnr_als::REC_SKIP_PTR].p + u0;
-  hipLaunchKernelGGL(gather_rows_kernel<T>, dim3((unsigned)((nb * k + 255) / 256)), dim3(256), 0, h->stream, (const T *)h->factors[YCNR_BY_USER],
+  hipLaunchKernelGGL(gather_rows_kernel<T>, dim3((unsigned)((nb * k + 255) / 256)), dim3(256), 0, h->stream, (const T *)users,
                      (const int32_t *)h->rec[ycnr_als::REC_USER_IDS].p + u0, nb, k, rows);
   const unsigned ublk = (unsigned)((nb + 15) / 16);
   const unsigned yblk = (unsigned)std::max<int64_t>(1, std::min<int64_t>((totalItems + 63) / 64, (8 * device_cus() + ublk - 1) / ublk));
@@ -2553,37 +2558,26 @@ void launch_scores_select(ycnr_als *h, int64_t u0, int64_t nb, bool valu, bool a
                      (int32_t *)h->rec[ycnr_als::REC_IDS].p + u0 * limit, (double *)h->rec[ycnr_als::REC_PRED].p + u0 * limit,
                      (int32_t *)h->rec[ycnr_als::REC_CNT].p + u0);
 }
-}  // namespace
-}  // extern "C++"
 
-int ycnr_als_recommend(ycnr_als *h, int64_t nUsers, const int32_t *userIds, const int64_t *skipPtr, const int32_t *skipIds,
-                       double globalAvgShift, double minRecommendRating, int32_t limit, int32_t *outIds, double *outPredict,
-                       int32_t *outCount, double *deviceMs) {
-  if (!h) return fail(YCNR_ERR_INVALID, "null handle");
-  if (nUsers < 0 || limit < 1 || limit > 4096) return fail(YCNR_ERR_INVALID, "ycnr_als_recommend: bad nUsers / limit");
-  if (nUsers == 0) {
-    if (deviceMs) *deviceMs = 0.0;
-    return YCNR_OK;
-  }
-  if (!userIds || !skipPtr || !outIds || !outPredict || !outCount) return fail(YCNR_ERR_INVALID, "ycnr_als_recommend: null argument");
-  if (skipPtr[0] != 0) return fail(YCNR_ERR_INVALID, "ycnr_als_recommend: skipPtr[0] != 0");
-  for (int64_t u = 0; u < nUsers; ++u) {
-    if (userIds[u] < 0 || userIds[u] >= h->opt.totalUsersCount)
-      return fail(YCNR_ERR_INVALID, "ycnr_als_recommend: user id %d at position %lld is outside [0, %lld)", userIds[u], (long long)u,
-                  (long long)h->opt.totalUsersCount);
-    if (skipPtr[u + 1] > skipPtr[u] && !skipIds) return fail(YCNR_ERR_INVALID, "ycnr_als_recommend: null skipIds");
-    if (skipPtr[u + 1] < skipPtr[u]) return fail(YCNR_ERR_INVALID, "ycnr_als_recommend: skipPtr decreases at user %lld", (long long)u);
-    for (int64_t q = skipPtr[u] + 1; q < skipPtr[u + 1]; ++q)
-      if (skipIds[q] <= skipIds[q - 1])
-        return fail(YCNR_ERR_INVALID, "ycnr_als_recommend: skip ids of user %lld are not strictly ascending", (long long)u);
-  }
+// The validated request of ycnr_als_recommend / ycnr_als_recommend_for_ratings on the handle's stream: top-N of the rows
+// userIds[.] of `users` (a device matrix [. x factorsCount]: the handle's user matrix, or the rows a fold-in has just solved
+// with userIds == null = rows 0 .. nUsers - 1).  started: the caller has recorded recEv[0] (its own kernels count into deviceMs).
+// dStatus (may be null): users with a non-zero status get an empty list.  beforeSync (may be empty): further copies to the host.
+int recommend_run(ycnr_als *h, const void *users, int64_t nUsers, const int32_t *userIds, const int64_t *skipPtr, const int32_t *skipIds,
+                  double globalAvgShift, double minRecommendRating, int32_t limit, int32_t *outIds, double *outPredict, int32_t *outCount,
+                  double *deviceMs, bool started, const int32_t *dStatus, const std::function<int()> &beforeSync) {
   const int64_t nSkip = skipPtr[nUsers];
   const int k = h->opt.factorsCount;
   const int64_t totalItems = h->opt.totalItemsCount;
   const size_t ts = h->ts();
   const int take = limit - 1;  // lib/YcnrController.js:268-269
   HIP_TRY(hipSetDevice(h->opt.device));
+  for (hipEvent_t &ev : h->recEv)
+    if (!ev) HIP_TRY(hipEventCreate(&ev));
   if (take == 0) {  // the reference returns nothing; still ordered behind the half-steps in flight
+    if (started) HIP_TRY(hipEventRecord(h->recEv[1], h->stream));
+    if (beforeSync)
+      if (int rc = beforeSync()) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
     for (int64_t u = 0; u < nUsers; ++u) {
       outIds[u] = -1;
@@ -2591,6 +2585,11 @@ int ycnr_als_recommend(ycnr_als *h, int64_t nUsers, const int32_t *userIds, cons
       outCount[u] = 0;
     }
     if (deviceMs) *deviceMs = 0.0;
+    if (deviceMs && started) {
+      float ms = 0;
+      HIP_TRY(hipEventElapsedTime(&ms, h->recEv[0], h->recEv[1]));
+      *deviceMs = ms;
+    }
     return YCNR_OK;
   }
   // the same choice of score kernel as ycnr_recommend_items, so that the predicts are the same bits -- its A/B switch
@@ -2623,31 +2622,41 @@ int ycnr_als_recommend(ycnr_als *h, int64_t nUsers, const int32_t *userIds, cons
     if (int rc = rec_reserve(h->rec[A::REC_ROWS], (size_t)batch * k * ts)) return rc;
     if (int rc = rec_reserve(h->rec[A::REC_SCORES], (size_t)batch * totalItems * 8)) return rc;
   }
-  for (hipEvent_t &ev : h->recEv)
-    if (!ev) HIP_TRY(hipEventCreate(&ev));
   // everything below is enqueued on the handle's stream: behind the half-steps in flight, like ycnr_als_rmse
-  HIP_TRY(hipMemcpyAsync(h->rec[A::REC_USER_IDS].p, userIds, (size_t)nUsers * 4, hipMemcpyHostToDevice, h->stream));
+  if (userIds) {
+    HIP_TRY(hipMemcpyAsync(h->rec[A::REC_USER_IDS].p, userIds, (size_t)nUsers * 4, hipMemcpyHostToDevice, h->stream));
+  } else {
+    hipLaunchKernelGGL(foldin_iota_kernel, dim3((unsigned)((nUsers + 255) / 256)), dim3(256), 0, h->stream, (int32_t *)h->rec[A::REC_USER_IDS].p, nUsers);
+    HIP_TRY(hipGetLastError());
+  }
   HIP_TRY(hipMemcpyAsync(h->rec[A::REC_SKIP_PTR].p, skipPtr, (size_t)(nUsers + 1) * 8, hipMemcpyHostToDevice, h->stream));
   if (nSkip) HIP_TRY(hipMemcpyAsync(h->rec[A::REC_SKIP].p, skipIds, (size_t)nSkip * 4, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipEventRecord(h->recEv[0], h->stream));
+  if (!started) HIP_TRY(hipEventRecord(h->recEv[0], h->stream));
   const double thr = minRecommendRating < -DBL_MAX ? -DBL_MAX : minRecommendRating;  // (-inf is "out" in the score matrix: it never competes)
   const size_t lds = std::max<size_t>(16 * kp * ts, (size_t)64 * take * 12);
   for (int64_t u0 = 0; u0 < nUsers; u0 += batch) {
     const int64_t nb = std::min(batch, nUsers - u0);
     if (fused) {
-      if (h->opt.dtype == YCNR_F32) launch_topn<float>(h, u0, nb, (unsigned)parts_of(nb), lds, globalAvgShift, thr, take, limit);
-      else launch_topn<double>(h, u0, nb, (unsigned)parts_of(nb), lds, globalAvgShift, thr, take, limit);
+      if (h->opt.dtype == YCNR_F32) launch_topn<float>(h, users, u0, nb, (unsigned)parts_of(nb), lds, globalAvgShift, thr, take, limit);
+      else launch_topn<double>(h, users, u0, nb, (unsigned)parts_of(nb), lds, globalAvgShift, thr, take, limit);
     } else {
-      if (h->opt.dtype == YCNR_F32) launch_scores_select<float>(h, u0, nb, valu, nSkip > 0, globalAvgShift, minRecommendRating, take, limit);
-      else launch_scores_select<double>(h, u0, nb, valu, nSkip > 0, globalAvgShift, minRecommendRating, take, limit);
+      if (h->opt.dtype == YCNR_F32) launch_scores_select<float>(h, users, u0, nb, valu, nSkip > 0, globalAvgShift, minRecommendRating, take, limit);
+      else launch_scores_select<double>(h, users, u0, nb, valu, nSkip > 0, globalAvgShift, minRecommendRating, take, limit);
     }
     hipError_t le = hipGetLastError();
     if (le != hipSuccess) return fail(YCNR_ERR_HIP, "recommend launch: %s", hipGetErrorString(le));
+  }
+  if (dStatus) {
+    hipLaunchKernelGGL(foldin_clear_lists_kernel, dim3((unsigned)((nUsers * limit + 255) / 256)), dim3(256), 0, h->stream, dStatus, nUsers, (int)limit,
+                       (int32_t *)h->rec[A::REC_IDS].p, (double *)h->rec[A::REC_PRED].p, (int32_t *)h->rec[A::REC_CNT].p);
+    HIP_TRY(hipGetLastError());
   }
   HIP_TRY(hipEventRecord(h->recEv[1], h->stream));
   HIP_TRY(hipMemcpyAsync(outIds, h->rec[A::REC_IDS].p, (size_t)nUsers * limit * 4, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipMemcpyAsync(outPredict, h->rec[A::REC_PRED].p, (size_t)nUsers * limit * 8, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipMemcpyAsync(outCount, h->rec[A::REC_CNT].p, (size_t)nUsers * 4, hipMemcpyDeviceToHost, h->stream));
+  if (beforeSync)
+    if (int rc = beforeSync()) return rc;
   HIP_TRY(hipStreamSynchronize(h->stream));
   if (deviceMs) {
     float ms = 0;
@@ -2655,6 +2664,206 @@ int ycnr_als_recommend(ycnr_als *h, int64_t nUsers, const int32_t *userIds, cons
     *deviceMs = ms;
   }
   return YCNR_OK;
+}
+
+// skip lists of a request: offsets from 0, never decreasing, ids strictly ascending per user
+int check_skip_lists(const char *what, int64_t nUsers, const int64_t *skipPtr, const int32_t *skipIds) {
+  if (skipPtr[0] != 0) return fail(YCNR_ERR_INVALID, "%s: skipPtr[0] != 0", what);
+  for (int64_t u = 0; u < nUsers; ++u) {
+    if (skipPtr[u + 1] > skipPtr[u] && !skipIds) return fail(YCNR_ERR_INVALID, "%s: null skipIds", what);
+    if (skipPtr[u + 1] < skipPtr[u]) return fail(YCNR_ERR_INVALID, "%s: skipPtr decreases at user %lld", what, (long long)u);
+    for (int64_t q = skipPtr[u] + 1; q < skipPtr[u + 1]; ++q)
+      if (skipIds[q] <= skipIds[q - 1]) return fail(YCNR_ERR_INVALID, "%s: skip ids of user %lld are not strictly ascending", what, (long long)u);
+  }
+  return YCNR_OK;
+}
+
+// ---- fold-in (foldin_kernels.hip.h): rows solved from ratings that arrive in the call ----
+
+// the request of ycnr_als_fold_in / ycnr_als_recommend_for_ratings; YCNR_ERR_INVALID before anything is touched
+int fold_check(const char *what, const ycnr_als *h, int side, int64_t nRows, const int64_t *rowPtr, const int32_t *indx, const void *vals,
+               const int32_t *storeIds) {
+  if (!rowPtr) return fail(YCNR_ERR_INVALID, "%s: null rowPtr", what);
+  if (rowPtr[0] != 0) return fail(YCNR_ERR_INVALID, "%s: rowPtr[0] != 0", what);
+  for (int64_t r = 0; r < nRows; ++r)
+    if (rowPtr[r + 1] < rowPtr[r]) return fail(YCNR_ERR_INVALID, "%s: rowPtr decreases at row %lld", what, (long long)r);
+  const int64_t total = rowPtr[nRows], fixedRows = h->rows(1 - side);
+  if (total > 0 && (!indx || !vals)) return fail(YCNR_ERR_INVALID, "%s: null indx / vals", what);
+  for (int64_t q = 0; q < total; ++q)
+    if (indx[q] < 0 || indx[q] >= fixedRows)
+      return fail(YCNR_ERR_INVALID, "%s: column id %d at position %lld is outside [0, %lld)", what, indx[q], (long long)q, (long long)fixedRows);
+  if (storeIds) {
+    std::vector<int32_t> ids(storeIds, storeIds + nRows);
+    std::sort(ids.begin(), ids.end());
+    if (nRows > 0 && (ids.front() < 0 || ids.back() >= h->rows(side)))
+      return fail(YCNR_ERR_INVALID, "%s: a store id is outside [0, %lld)", what, (long long)h->rows(side));
+    if (std::adjacent_find(ids.begin(), ids.end()) != ids.end()) return fail(YCNR_ERR_INVALID, "%s: a store id is repeated", what);
+  }
+  return YCNR_OK;
+}
+
+// factorsCount > 128: the step kernels out of place, as the level-1 portion op drives them (als_calc_portion): the plan of a
+// piece with every row in primal form, the solved rows into FOLD_ROWS, the fixed side = the handle's own device matrix
+template <typename T>
+int fold_launch_steps(ycnr_als *h, int side, int64_t nRows, const int64_t *rowPtr, double lambda) {
+  typedef ycnr_als A;
+  const int k = h->opt.factorsCount, dtype = h->opt.dtype;
+  const bool gen = is_gen(dtype, k) || k % 4 != 0;  // (float32 rows that are not 16-byte multiples: the any-k path, as in level 1)
+  const bool big = !gen;
+  const int nb = slab_nb(k);
+  const size_t slabElems = gen ? (size_t)gen_slab_elems(nb) : (size_t)wg_slab_floats(nb);
+  PlanParams P;
+  P.kind = gen ? kAnyK : kWorkgroup;
+  P.chunk = gen ? kGenChunk : kWgChunk;
+  P.fusedMax = big ? kWgFusedMax : 0;
+  P.k = k;
+  P.shuffle = P.sortSplit = false;
+  if (gen) P.arenaSlabs = gen_arena_slabs(slabElems * sizeof(T));
+  h->foldPlan = plan_piece(rowPtr, 0, nRows, P);  // (kept on the handle: its lists are the source of the copies below)
+  const PiecePlan &plan = h->foldPlan;
+  if (int rc = rec_reserve(h->rec[A::FOLD_UNITS], sizeof(Unit) * std::max<size_t>(1, plan.units.size()))) return rc;
+  if (int rc = rec_reserve(h->rec[A::FOLD_SPLIT], sizeof(SplitRow) * std::max<size_t>(1, plan.split.size()))) return rc;
+  if (int rc = rec_reserve(h->rec[A::FOLD_SLABS], sizeof(T) * std::max<size_t>(1, (size_t)plan.arenaSlabs * slabElems))) return rc;
+  if (int rc = rec_reserve(h->rec[A::FOLD_ERR], sizeof(ErrInfo))) return rc;
+  if (!plan.units.empty())
+    HIP_TRY(hipMemcpyAsync(h->rec[A::FOLD_UNITS].p, plan.units.data(), sizeof(Unit) * plan.units.size(), hipMemcpyHostToDevice, h->stream));
+  if (!plan.split.empty())
+    HIP_TRY(hipMemcpyAsync(h->rec[A::FOLD_SPLIT].p, plan.split.data(), sizeof(SplitRow) * plan.split.size(), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemsetAsync(h->rec[A::FOLD_ERR].p, 0, sizeof(ErrInfo), h->stream));
+  StepArgs<T> a{(const Unit *)h->rec[A::FOLD_UNITS].p, (const SplitRow *)h->rec[A::FOLD_SPLIT].p, (const int32_t *)h->rec[A::FOLD_INDX].p,
+                (const T *)h->rec[A::FOLD_VALS].p, (const T *)h->factors[1 - side], (const T *)h->dZeros, (T *)h->rec[A::FOLD_ROWS].p,
+                (T *)h->rec[A::FOLD_SLABS].p, (ErrInfo *)h->rec[A::FOLD_ERR].p, lambda, k, 0, 0, 0u};
+  if (gen) return launch_step_gen<T>(a, plan.genBatches, h->stream, nullptr, DualPlan());
+  if constexpr (std::is_same<T, float>::value)
+    return launch_step_big(a, (int64_t)plan.units.size(), plan.nSlabs, (int64_t)plan.split.size(), h->stream, nullptr, DualPlan());
+  return fail(YCNR_ERR_UNSUPPORTED, "fold-in: no kernel for factorsCount %d", k);
+}
+
+// Uploads the (validated) request and enqueues its solve on the handle's stream; records recEv[0] in front of the kernels.
+// Afterwards FOLD_ROWS holds nRows x factorsCount solved rows and FOLD_STATUS their status, both on the device.
+template <typename T>
+int fold_enqueue(ycnr_als *h, int side, int64_t nRows, const int64_t *rowPtr, const int32_t *indx, const void *vals, const int32_t *storeIds) {
+  typedef ycnr_als A;
+  const int k = h->opt.factorsCount;
+  const int64_t total = rowPtr[nRows];
+  const double lambda = side == YCNR_BY_USER ? h->opt.userFactReg : h->opt.itemFactReg;
+  if (int rc = rec_reserve(h->rec[A::FOLD_PTR], (size_t)(nRows + 1) * 8)) return rc;
+  if (int rc = rec_reserve(h->rec[A::FOLD_INDX], std::max<size_t>((size_t)total * 4 + 64, 8))) return rc;
+  if (int rc = rec_reserve(h->rec[A::FOLD_VALS], std::max<size_t>((size_t)total * sizeof(T) + 64, 8))) return rc;
+  if (int rc = rec_reserve(h->rec[A::FOLD_ROWS], (size_t)nRows * k * sizeof(T))) return rc;
+  if (int rc = rec_reserve(h->rec[A::FOLD_STATUS], (size_t)nRows * 4)) return rc;
+  if (storeIds)
+    if (int rc = rec_reserve(h->rec[A::FOLD_STORE], (size_t)nRows * 4)) return rc;
+  for (hipEvent_t &ev : h->recEv)
+    if (!ev) HIP_TRY(hipEventCreate(&ev));
+  // everything below is enqueued on the handle's stream: behind the half-steps in flight, like ycnr_als_rmse
+  HIP_TRY(hipMemcpyAsync(h->rec[A::FOLD_PTR].p, rowPtr, (size_t)(nRows + 1) * 8, hipMemcpyHostToDevice, h->stream));
+  if (total) {
+    HIP_TRY(hipMemcpyAsync(h->rec[A::FOLD_INDX].p, indx, (size_t)total * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->rec[A::FOLD_VALS].p, vals, (size_t)total * sizeof(T), hipMemcpyHostToDevice, h->stream));
+  }
+  if (storeIds) HIP_TRY(hipMemcpyAsync(h->rec[A::FOLD_STORE].p, storeIds, (size_t)nRows * 4, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipEventRecord(h->recEv[0], h->stream));
+  T *store = storeIds ? (T *)h->factors[side] : nullptr;
+  if (k <= kFoldMaxK) {
+    FoldArgs<T> fa{(const int64_t *)h->rec[A::FOLD_PTR].p, (const int32_t *)h->rec[A::FOLD_INDX].p, (const T *)h->rec[A::FOLD_VALS].p,
+                   (const T *)h->factors[1 - side], (T *)h->rec[A::FOLD_ROWS].p, (int32_t *)h->rec[A::FOLD_STATUS].p, store,
+                   (const int32_t *)h->rec[A::FOLD_STORE].p, lambda, k};
+    const size_t lds = foldin_lds_bytes(k);
+    if (int rc = set_max_lds(reinterpret_cast<const void *>(als_foldin_kernel<T>), lds)) return rc;
+    hipLaunchKernelGGL(als_foldin_kernel<T>, dim3((unsigned)nRows), dim3(256), lds, h->stream, fa);
+    HIP_TRY(hipGetLastError());
+    return YCNR_OK;
+  }
+  if (total > 0)
+    if (int rc = fold_launch_steps<T>(h, side, nRows, rowPtr, lambda)) return rc;
+  if (total == 0) {
+    if (int rc = rec_reserve(h->rec[A::FOLD_ERR], sizeof(ErrInfo))) return rc;
+    HIP_TRY(hipMemsetAsync(h->rec[A::FOLD_ERR].p, 0, sizeof(ErrInfo), h->stream));
+  }
+  hipLaunchKernelGGL(foldin_finish_kernel<T>, dim3((unsigned)nRows), dim3(256), 0, h->stream, (const int64_t *)h->rec[A::FOLD_PTR].p,
+                     (const ErrInfo *)h->rec[A::FOLD_ERR].p, nRows, k, (T *)h->rec[A::FOLD_ROWS].p, (int32_t *)h->rec[A::FOLD_STATUS].p, store,
+                     (const int32_t *)h->rec[A::FOLD_STORE].p);
+  HIP_TRY(hipGetLastError());
+  return YCNR_OK;
+}
+int fold_enqueue_any(ycnr_als *h, int side, int64_t nRows, const int64_t *rowPtr, const int32_t *indx, const void *vals, const int32_t *storeIds) {
+  return h->opt.dtype == YCNR_F64 ? fold_enqueue<double>(h, side, nRows, rowPtr, indx, vals, storeIds)
+                                  : fold_enqueue<float>(h, side, nRows, rowPtr, indx, vals, storeIds);
+}
+}  // namespace
+}  // extern "C++"
+
+int ycnr_als_recommend(ycnr_als *h, int64_t nUsers, const int32_t *userIds, const int64_t *skipPtr, const int32_t *skipIds,
+                       double globalAvgShift, double minRecommendRating, int32_t limit, int32_t *outIds, double *outPredict,
+                       int32_t *outCount, double *deviceMs) {
+  if (!h) return fail(YCNR_ERR_INVALID, "null handle");
+  if (nUsers < 0 || limit < 1 || limit > 4096) return fail(YCNR_ERR_INVALID, "ycnr_als_recommend: bad nUsers / limit");
+  if (nUsers == 0) {
+    if (deviceMs) *deviceMs = 0.0;
+    return YCNR_OK;
+  }
+  if (!userIds || !skipPtr || !outIds || !outPredict || !outCount) return fail(YCNR_ERR_INVALID, "ycnr_als_recommend: null argument");
+  for (int64_t u = 0; u < nUsers; ++u)
+    if (userIds[u] < 0 || userIds[u] >= h->opt.totalUsersCount)
+      return fail(YCNR_ERR_INVALID, "ycnr_als_recommend: user id %d at position %lld is outside [0, %lld)", userIds[u], (long long)u,
+                  (long long)h->opt.totalUsersCount);
+  if (int rc = check_skip_lists("ycnr_als_recommend", nUsers, skipPtr, skipIds)) return rc;
+  return recommend_run(h, h->factors[YCNR_BY_USER], nUsers, userIds, skipPtr, skipIds, globalAvgShift, minRecommendRating, limit, outIds, outPredict,
+                       outCount, deviceMs, false, nullptr, std::function<int()>());
+}
+
+int ycnr_als_fold_in(ycnr_als *h, int side, int64_t nRows, const int64_t *rowPtr, const int32_t *indx, const void *vals,
+                     const int32_t *storeIds, void *outRows, int32_t *outStatus, double *deviceMs) {
+  if (!h) return fail(YCNR_ERR_INVALID, "null handle");
+  if (side != YCNR_BY_USER && side != YCNR_BY_ITEM) return fail(YCNR_ERR_INVALID, "bad side %d", side);
+  if (nRows < 0 || nRows > 0x7fffffffLL) return fail(YCNR_ERR_INVALID, "ycnr_als_fold_in: bad nRows");
+  if (nRows == 0) {
+    if (deviceMs) *deviceMs = 0.0;
+    return YCNR_OK;
+  }
+  if (!outRows || !outStatus) return fail(YCNR_ERR_INVALID, "ycnr_als_fold_in: null argument");
+  if (int rc = fold_check("ycnr_als_fold_in", h, side, nRows, rowPtr, indx, vals, storeIds)) return rc;
+  HIP_TRY(hipSetDevice(h->opt.device));
+  if (int rc = fold_enqueue_any(h, side, nRows, rowPtr, indx, vals, storeIds)) return rc;
+  typedef ycnr_als A;
+  HIP_TRY(hipEventRecord(h->recEv[1], h->stream));
+  HIP_TRY(hipMemcpyAsync(outRows, h->rec[A::FOLD_ROWS].p, (size_t)nRows * h->opt.factorsCount * h->ts(), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(outStatus, h->rec[A::FOLD_STATUS].p, (size_t)nRows * 4, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (deviceMs) {
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, h->recEv[0], h->recEv[1]));
+    *deviceMs = ms;
+  }
+  return YCNR_OK;
+}
+
+int ycnr_als_recommend_for_ratings(ycnr_als *h, int64_t nUsers, const int64_t *ratPtr, const int32_t *ratIds, const void *ratVals,
+                                   const int64_t *skipPtr, const int32_t *skipIds, double globalAvgShift, double minRecommendRating,
+                                   int32_t limit, int32_t *outIds, double *outPredict, int32_t *outCount, void *outRows, int32_t *outStatus,
+                                   double *deviceMs) {
+  if (!h) return fail(YCNR_ERR_INVALID, "null handle");
+  if (nUsers < 0 || nUsers > 0x7fffffffLL || limit < 1 || limit > 4096) return fail(YCNR_ERR_INVALID, "ycnr_als_recommend_for_ratings: bad nUsers / limit");
+  if (nUsers == 0) {
+    if (deviceMs) *deviceMs = 0.0;
+    return YCNR_OK;
+  }
+  if (!skipPtr || !outIds || !outPredict || !outCount || !outStatus) return fail(YCNR_ERR_INVALID, "ycnr_als_recommend_for_ratings: null argument");
+  if (int rc = fold_check("ycnr_als_recommend_for_ratings", h, YCNR_BY_USER, nUsers, ratPtr, ratIds, ratVals, nullptr)) return rc;
+  if (int rc = check_skip_lists("ycnr_als_recommend_for_ratings", nUsers, skipPtr, skipIds)) return rc;
+  HIP_TRY(hipSetDevice(h->opt.device));
+  if (int rc = fold_enqueue_any(h, YCNR_BY_USER, nUsers, ratPtr, ratIds, ratVals, nullptr)) return rc;
+  typedef ycnr_als A;
+  const size_t rowBytes = (size_t)nUsers * h->opt.factorsCount * h->ts();
+  // the solved rows never leave the device between the two halves; their copy to the host rides behind the top-N
+  auto copies = [&]() -> int {
+    if (outRows) HIP_TRY(hipMemcpyAsync(outRows, h->rec[A::FOLD_ROWS].p, rowBytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(outStatus, h->rec[A::FOLD_STATUS].p, (size_t)nUsers * 4, hipMemcpyDeviceToHost, h->stream));
+    return YCNR_OK;
+  };
+  return recommend_run(h, h->rec[A::FOLD_ROWS].p, nUsers, nullptr, skipPtr, skipIds, globalAvgShift, minRecommendRating, limit, outIds, outPredict,
+                       outCount, deviceMs, true, (const int32_t *)h->rec[A::FOLD_STATUS].p, copies);
 }
 
 // ---- multi-GPU exchange (comm_impl.hip.h) ----

@@ -323,6 +323,43 @@ class EmfLord extends EmfMaster {
     return als.recommend(this.handle, ids, skipLists, this.globalAvgShift || 0, thr, limit || 20);
   }
 
+  /**
+   * recommendItemsForUser for users WITHOUT a trained row -- the case the reference gives up on ("User hasn't list yet",
+   * lib/YcnrController.js:275-280): ratings[i] = [[itemId, rating], ...] of request user i, item ids 1-based.  Each row is
+   * solved on the device from these ratings against the item factors the handle holds (fold-in) and ranked there; nothing is
+   * stored.  Left out: the given items and unratedItems[i] (0-based, as in recommendItemsForUsers); shift, threshold and
+   * the returned lists are those of recommendItemsForUsers.  Needs only the item matrix: works with itemStepSharding 'bands'.
+   */
+  recommendItemsForRatings(ratings, limit, minRecommendRating, unratedItems) {
+    if (this.handle === null) throw new Error('recommendItemsForRatings: prepareToTrain has not been called');
+    if (unratedItems && unratedItems.length != ratings.length) throw new Error('recommendItemsForRatings: unratedItems needs one entry (or null) per user');
+    const skipLists = ratings.map((row, i) => {
+      const seen = new Set();
+      for (const p of row) seen.add(Number(p[0]) - 1);
+      if (unratedItems && unratedItems[i]) for (const id0 of unratedItems[i]) seen.add(Number(id0));
+      return Int32Array.from(seen).sort();
+    });
+    const thr = (minRecommendRating === undefined || minRecommendRating === null) ? this.minRecommendRating : minRecommendRating;
+    return als.recommendForRatings(this.handle, ratings, skipLists, this.factorsCount, this.totalItemsCount, this.TypedArrayClass,
+      this.globalAvgShift || 0, thr, limit || 20);
+  }
+
+  /**
+   * Factor rows of new users (stepType 'byUser': rows[i] = [[itemId, rating], ...]) or new items ('byItem': [[userId, rating], ...]),
+   * ids 1-based, solved on the device against the opposite matrix the handle holds.  storeIds (0-based rows of that side, one
+   * per request row): also write the solved rows into this process's matrix, which makes a new item recommendable and a new
+   * user reachable by recommendItemsForUsers.  Returns {rows, status} (status 0 solved / 1 not positive definite / 2 no ratings).
+   */
+  foldIn(stepType, rows, storeIds) {
+    if (this.handle === null) throw new Error('foldIn: prepareToTrain has not been called');
+    if (stepType != 'byUser' && stepType != 'byItem') throw new Error("foldIn: stepType must be 'byUser' or 'byItem'");
+    const side = als.stepSide[stepType];
+    if (side == 1 && this.bands && this.options.world > 1)
+      throw new Error("foldIn('byItem'): with itemStepSharding 'bands' the user matrix is not replicated on every rank; " +
+        'recommend from a Lord that holds both matrices');
+    return als.foldIn(this.handle, side, rows, this.factorsCount, side == 0 ? this.totalItemsCount : this.totalUsersCount, this.TypedArrayClass, storeIds);
+  }
+
   /** @param string stepType 'rmseValidate', 'rmseTest' (EmfLord.js:1043-1081) */
   calcRmse(stepType, useGlobalAvgShift) {
     if (useGlobalAvgShift && this.options.alg != 'als')

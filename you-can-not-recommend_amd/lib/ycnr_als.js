@@ -159,5 +159,59 @@
     return out;
   };
 
+  // rows[i] = [[id1, rating], ...] with 1-based ids (the reference's tables) -> request CSR with 0-based ids
+  function requestCsr(rows, cols, F) {
+    var n = rows.length, ptr = new Float64Array(n + 1), i, j;
+    for (i = 0; i < n; i++) ptr[i + 1] = ptr[i] + rows[i].length;
+    var ids = new Int32Array(ptr[n]), vals = new F(ptr[n]);
+    for (i = 0; i < n; i++) {
+      for (j = 0; j < rows[i].length; j++) {
+        var id0 = Number(rows[i][j][0]) - 1;
+        if (!(id0 >= 0 && id0 < cols)) throw new Error('rating of an id outside [1, ' + cols + ']');
+        ids[ptr[i] + j] = id0;
+        vals[ptr[i] + j] = rows[i][j][1];
+      }
+    }
+    return { ptr: ptr, ids: ids, vals: vals };
+  }
+  als.requestCsr = requestCsr;
+
+  /**
+   * Factor rows of NEW users (side 0: rows[i] = [[itemId, rating], ...]) or new items (side 1: [[userId, rating], ...]),
+   * ids 1-based, solved on the device from these ratings against the opposite matrix the handle holds (ycnr_als_fold_in) --
+   * the users the reference gives up on (lib/YcnrController.js:275-280). F: the handle's typed-array class; cols: rows of the
+   * opposite side; storeIds (optional): 0-based rows of the handle's own matrix of that side to write the solved rows to.
+   * Returns {rows: F(n * factorsCount), status: Int32Array(n)} (0 solved, 1 not positive definite, 2 no ratings).
+   */
+  als.foldIn = function (handle, side, rows, factorsCount, cols, F, storeIds) {
+    var q = requestCsr(rows, cols, F), n = rows.length;
+    var out = new F(n * factorsCount), status = new Int32Array(n);
+    native.foldIn(handle, side, q.ptr, q.ids, q.vals, storeIds ? Int32Array.from(storeIds) : null, out, status);
+    return { rows: out, status: status };
+  };
+
+  /**
+   * foldIn of the user side + the top-N of the solved rows without a host round trip (ycnr_als_recommend_for_ratings).
+   * ratings[i] = [[itemId, rating], ...] (1-based); skipLists[i]: SORTED UNIQUE 0-based item ids to leave out.
+   * Returns per user [{predict, id}] (id 1-based); users without ratings get an empty list.
+   */
+  als.recommendForRatings = function (handle, ratings, skipLists, factorsCount, totalItems, F, globalAvgShift, minRecommendRating, limit) {
+    limit = limit || 20;
+    var q = requestCsr(ratings, totalItems, F), n = ratings.length, skipPtr = new Float64Array(n + 1), i, j;
+    for (i = 0; i < n; i++) skipPtr[i + 1] = skipPtr[i] + skipLists[i].length;
+    var skipIds = new Int32Array(skipPtr[n]);
+    for (i = 0; i < n; i++) skipIds.set(skipLists[i], skipPtr[i]);
+    var ids = new Int32Array(n * limit), pred = new Float64Array(n * limit), cnt = new Int32Array(n);
+    var rows = new F(n * factorsCount), status = new Int32Array(n);
+    native.recommendForRatings(handle, q.ptr, q.ids, q.vals, skipPtr, skipIds, globalAvgShift || 0, minRecommendRating, limit, ids, pred, cnt, rows, status);
+    var out = [];
+    for (i = 0; i < n; i++) {
+      var recItems = [];
+      for (j = 0; j < cnt[i]; j++) recItems.push({ predict: pred[i * limit + j], id: ids[i * limit + j] + 1 });
+      out.push(recItems);
+    }
+    return out;
+  };
+
   module.exports = als;
 }());

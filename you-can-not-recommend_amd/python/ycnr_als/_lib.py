@@ -48,7 +48,7 @@ EXPORTS = [
     "ycnr_als_bind_factors", "ycnr_als_step", "ycnr_als_step_async", "ycnr_als_sync",
     "ycnr_als_last_step_info", "ycnr_als_step_info_of", "ycnr_als_rmse",
     "ycnr_split_to_sets", "ycnr_rating_stats", "ycnr_csr_from_triplets", "ycnr_csr_transpose",
-    "ycnr_recommend_items", "ycnr_als_recommend",
+    "ycnr_recommend_items", "ycnr_als_recommend", "ycnr_als_fold_in", "ycnr_als_recommend_for_ratings",
     "ycnr_comm_unique_id", "ycnr_als_comm_init", "ycnr_als_comm_destroy", "ycnr_als_set_ratings_sharded",
     "ycnr_als_exchange", "ycnr_als_broadcast_factors", "ycnr_als_allreduce_sum", "ycnr_als_comm_selftest",
     "ycnr_als_comm_info", "ycnr_als_last_rmse_ms", "ycnr_als_set_ratings_banded", "ycnr_als_defer_exchange",
@@ -163,6 +163,10 @@ def load():
     L.ycnr_recommend_items.argtypes = [i32, i32, i64, vp, i64, vp, vp, vp, dbl, dbl, i32, vp, vp, vp, C.POINTER(dbl)]
     L.ycnr_als_recommend.restype = i32
     L.ycnr_als_recommend.argtypes = [vp, i64, vp, vp, vp, dbl, dbl, i32, vp, vp, vp, C.POINTER(dbl)]
+    L.ycnr_als_fold_in.restype = i32
+    L.ycnr_als_fold_in.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, vp, C.POINTER(dbl)]
+    L.ycnr_als_recommend_for_ratings.restype = i32
+    L.ycnr_als_recommend_for_ratings.argtypes = [vp, i64, vp, vp, vp, vp, vp, dbl, dbl, i32, vp, vp, vp, vp, vp, C.POINTER(dbl)]
     L.ycnr_csr_transpose.restype = i32
     L.ycnr_csr_transpose.argtypes = [i32, i64, i64, vp, vp, vp, vp, vp, vp, C.POINTER(dbl)]
     L.ycnr_comm_unique_id.restype = i32

@@ -339,6 +339,16 @@ class HipBackend:
         self.torch.cuda.current_stream(self.device).synchronize()  # (as step())
         return self.dev.recommend(user_ids, skip_ptr, skip_ids, shift, min_rating, limit)[:3]
 
+    def fold_in(self, side, row_ptr, indx, vals, store_ids=None):
+        """rows solved from ratings given in the call (ycnr_als_fold_in): (rows, status)"""
+        self.torch.cuda.current_stream(self.device).synchronize()  # (as step())
+        return self.dev.fold_in(side, row_ptr, indx, np.asarray(vals, self.dtype_np), store_ids)[:2]
+
+    def recommend_for_ratings(self, rat_ptr, rat_ids, rat_vals, skip_ptr, skip_ids, shift, min_rating, limit):
+        """fold-in of new users + top-N on the solved rows (ycnr_als_recommend_for_ratings): (ids, predicts, counts, rows, status)"""
+        self.torch.cuda.current_stream(self.device).synchronize()  # (as step())
+        return self.dev.recommend_for_ratings(rat_ptr, rat_ids, np.asarray(rat_vals, self.dtype_np), skip_ptr, skip_ids, shift, min_rating, limit)[:5]
+
     def destroy(self):
         self.dev.destroy()
 
@@ -811,6 +821,66 @@ class EmfLord:
         ptr, skip = self.recommendSkipLists(uid, unratedItems)
         ids, pred, cnt = self.backend.recommend(uid.astype(np.int32), ptr, skip, float(self.globalAvgShift), float(thr), int(limit))
         return [[{"id": int(ids[i, j]) + 1, "predict": float(pred[i, j])} for j in range(int(cnt[i]))] for i in range(len(uid))]
+
+    @staticmethod
+    def _request_csr(rows, cols):
+        """rows[i] = list of (id1, rating) with 1-based ids (the reference's tables) -> (rowPtr, 0-based ids, ratings)"""
+        ptr = np.zeros(len(rows) + 1, np.int64)
+        ptr[1:] = np.cumsum([len(r) for r in rows])
+        ids = np.array([int(p[0]) - 1 for r in rows for p in r], np.int64)
+        vals = np.array([float(p[1]) for r in rows for p in r], np.float64)
+        if len(ids) and (ids.min() < 0 or ids.max() >= cols):
+            raise ValueError("rating of an id outside [1, %d]" % cols)
+        return ptr, ids.astype(np.int32), vals
+
+    def recommendItemsForRatings(self, ratings, limit=20, minRecommendRating=None, unratedItems=None):
+        """recommendItemsForUser for users WITHOUT a trained row -- the case the reference gives up on ("User hasn't list yet",
+        lib/YcnrController.js:275-280): ratings[i] is the list of (itemId, rating) of request user i, item ids 1-based like the
+        reference's tables.  Each user's row is solved on the device from these ratings against the item factors the backend
+        holds (fold-in, one row of a half-step) and ranked there; nothing is stored.  The given items and unratedItems[i]
+        (0-based, as in recommendItemsForUsers) are left out; shift, threshold and the returned lists are those of
+        recommendItemsForUsers.  A user without ratings (or whose solve failed) gets an empty list.  Needs only the item
+        matrix, so it also works with itemStepSharding='bands'."""
+        if self.backend is None:
+            raise RuntimeError("recommendItemsForRatings: prepareToTrain has not been called")
+        if not hasattr(self.backend, "recommend_for_ratings"):
+            raise RuntimeError("recommendItemsForRatings: the backend has no recommend_for_ratings(); nothing is computed on the host")
+        n = len(ratings)
+        if unratedItems is not None and len(unratedItems) != n:
+            raise ValueError("recommendItemsForRatings: unratedItems needs one entry (or None) per user")
+        ptr, ids, vals = self._request_csr(ratings, self.totalItemsCount)
+        lists = []
+        for i in range(n):
+            parts = [ids[ptr[i]:ptr[i + 1]].astype(np.int64)]
+            if unratedItems is not None and unratedItems[i] is not None:
+                parts.append(np.asarray(unratedItems[i], np.int64).reshape(-1))
+            lists.append(np.unique(np.concatenate(parts)).astype(np.int32))
+        sptr = np.zeros(n + 1, np.int64)
+        sptr[1:] = np.cumsum([len(x) for x in lists])
+        skip = np.concatenate(lists) if lists else np.zeros(0, np.int32)
+        thr = self.minRecommendRating if minRecommendRating is None else minRecommendRating
+        out, pred, cnt = self.backend.recommend_for_ratings(ptr, ids, vals, sptr, skip, float(self.globalAvgShift), float(thr), int(limit))[:3]
+        return [[{"id": int(out[i, j]) + 1, "predict": float(pred[i, j])} for j in range(int(cnt[i]))] for i in range(n)]
+
+    def foldIn(self, stepType, rows, storeIds=None):
+        """Factor rows of new users (stepType 'byUser': rows[i] = list of (itemId, rating)) or new items ('byItem': (userId,
+        rating)), ids 1-based, solved on the device against the opposite matrix the backend holds.  storeIds (0-based row
+        ids of that side, one per request row): also write the solved rows into this rank's matrix, which makes a new item
+        recommendable and a new user reachable by recommendItemsForUsers.  Returns (rows [n x factorsCount], status [n]:
+        0 solved / 1 not positive definite / 2 no ratings)."""
+        if self.backend is None:
+            raise RuntimeError("foldIn: prepareToTrain has not been called")
+        if stepType not in ("byUser", "byItem"):
+            raise ValueError("foldIn: stepType must be 'byUser' or 'byItem'")
+        side = 0 if stepType == "byUser" else 1
+        if side == 1 and self.bands is not None and self.world > 1:
+            raise RuntimeError("foldIn('byItem'): with itemStepSharding='bands' the user matrix is not replicated on "
+                               "every rank; recommend from a Lord that holds both matrices (loadCalcResults on one rank)")
+        if not hasattr(self.backend, "fold_in"):
+            raise RuntimeError("foldIn: the backend has no fold_in(); nothing is computed on the host")
+        ptr, ids, vals = self._request_csr(rows, self.totalItemsCount if side == 0 else self.totalUsersCount)
+        st = None if storeIds is None else np.asarray(storeIds, np.int32).reshape(-1)
+        return self.backend.fold_in(side, ptr, ids, vals, st)[:2]
 
     def getCalcInfo(self):
         o = self.options

@@ -380,3 +380,51 @@ class AlsDevice:
                                          float(globalAvgShift), float(minRecommendRating), int(limit), ids.ctypes.data,
                                          pred.ctypes.data, cnt.ctypes.data, C.byref(ms)))
         return ids, pred, cnt, ms.value
+
+    def _request_csr(self, rowPtr, indx, vals):
+        rp = np.ascontiguousarray(rowPtr, np.int64).reshape(-1)
+        ix = np.ascontiguousarray(indx, np.int32).reshape(-1)
+        vl = np.ascontiguousarray(vals, self.dtype).reshape(-1)
+        if len(rp) < 1 or len(ix) != len(vl) or (len(rp) > 1 and rp[-1] > len(ix)):
+            raise ValueError("rowPtr / indx / vals do not describe one CSR")
+        return rp, ix, vl
+
+    def fold_in(self, side, rowPtr, indx, vals, storeIds=None):
+        """Rows of NEW users (side 'byUser': indx are item ids) or new items solved from the ratings given here against the
+        fixed opposite matrix the handle holds (ycnr_als_fold_in); the CSR is relative to the request.  storeIds: also
+        write the rows with status 0 into the handle's own matrix of `side` at these row ids.  Runs behind the half-steps
+        in flight.  Returns (rows [n x k], status [n]: 0 solved / 1 not positive definite / 2 no ratings, kernel ms)."""
+        rp, ix, vl = self._request_csr(rowPtr, indx, vals)
+        n = len(rp) - 1
+        st = None if storeIds is None else np.ascontiguousarray(storeIds, np.int32).reshape(-1)
+        if st is not None and len(st) != n:
+            raise ValueError("storeIds needs one id per request row")
+        rows = np.zeros((n, self.k), self.dtype)
+        status = np.zeros(n, np.int32)
+        ms = C.c_double(0.0)
+        check(self._L.ycnr_als_fold_in(self._h, SIDES[side], n, rp.ctypes.data, ix.ctypes.data if len(ix) else None,
+                                       vl.ctypes.data if len(vl) else None, None if st is None else st.ctypes.data,
+                                       rows.ctypes.data, status.ctypes.data, C.byref(ms)))
+        return rows, status, ms.value
+
+    def recommend_for_ratings(self, ratPtr, ratIds, ratVals, skipPtr, skipIds, globalAvgShift=0.0, minRecommendRating=7.0, limit=20):
+        """fold_in('byUser') of the request's ratings, then recommend() on the solved rows without a host round trip
+        (ycnr_als_recommend_for_ratings).  Returns (ids [n x limit] with -1 padding, predicts, counts, rows, status, kernel ms);
+        users whose status is not 0 get count 0."""
+        rp, ix, vl = self._request_csr(ratPtr, ratIds, ratVals)
+        n = len(rp) - 1
+        sp = np.ascontiguousarray(skipPtr, np.int64)
+        sk = np.ascontiguousarray(skipIds, np.int32)
+        if len(sp) != n + 1:
+            raise ValueError("skipPtr needs one entry per requested user plus one")
+        ids = np.full((n, max(int(limit), 0)), -1, np.int32)
+        pred = np.zeros((n, max(int(limit), 0)), np.float64)
+        cnt = np.zeros(n, np.int32)
+        rows = np.zeros((n, self.k), self.dtype)
+        status = np.zeros(n, np.int32)
+        ms = C.c_double(0.0)
+        check(self._L.ycnr_als_recommend_for_ratings(self._h, n, rp.ctypes.data, ix.ctypes.data if len(ix) else None,
+                                                     vl.ctypes.data if len(vl) else None, sp.ctypes.data, sk.ctypes.data if len(sk) else None,
+                                                     float(globalAvgShift), float(minRecommendRating), int(limit), ids.ctypes.data,
+                                                     pred.ctypes.data, cnt.ctypes.data, rows.ctypes.data, status.ctypes.data, C.byref(ms)))
+        return ids, pred, cnt, rows, status, ms.value
