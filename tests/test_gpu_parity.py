@@ -66,12 +66,13 @@ def test_golden_portion(als, oracle, name):
     assert np.allclose(out, z["rmse_out"], rtol=1e-6 if dt == np.float32 else 1e-12)
 
 
-@pytest.mark.parametrize("k,dt", [(20, np.float32), (100, np.float32), (100, np.float64), (200, np.float32)])
+@pytest.mark.parametrize("k,dt", [(20, np.float32), (100, np.float32), (100, np.float64), (200, np.float32),
+                                  (130, np.float32), (136, np.float64)])  # the last two: the any-k path (float32 rows that are no 16-byte multiple; float64 above 128)
 def test_portion_ops_keep_state_and_pinned_matrix(als, k, dt):
     """Level 1 as the reference would drive it: many portions per half-step on one thread (stream and
     device buffers are reused), with and without the step's fixed matrix pinned on the device
     (ycnr_{s,d}AlsPinFixedFactors) -- bit-identical results either way, against float64, including
-    k > 128 through the workgroup-per-row kernels; a changed matrix must be pinned again."""
+    k > 128 through the workgroup-per-row kernels and the any-k kernels; a changed matrix must be pinned again."""
     import ycnr_als
     users, items = 600, 900
     bu, _, U, V = make_problem(users, items, k, density=0.06, seed=5 + k, dtype=dt, empty_rows=(7,))

@@ -33,7 +33,8 @@ namespace ycnr {
 constexpr int kGenWaves = 4;
 constexpr int kGenThreads = kGenWaves * 64;
 
-__host__ __device__ constexpr int64_t gen_slab_elems(int nb) { return (int64_t)tile_count(nb) * 256 + (int64_t)nb * 16; }
+// gen_slab_elems and the sizes of the Gramian and the solves (gen_items ... gen_solve_lds_bytes, kGenSq, kGenGramMaxWaves,
+// kGenPanelLdsMax): step_policy.h, where choose_gen sizes a launch from them
 
 template <typename T>
 struct GenArgs {
@@ -72,8 +73,6 @@ __device__ __forceinline__ void gen_st_tile(T *tile, int lane, const typename Mf
 // 4 s + g; the row pitch P puts the four lane groups on different banks).  float32: 4 x 4 tiles, five passes of eight
 // waves at k = 512; float64: 2 x 4, three passes of seven at k = 256.
 // 200 K x 20 K, 20 M ratings, per iteration: k = 512 float32 902 (strips) -> 606 (squares from cache) -> see DESIGN.md.
-constexpr int kGenSq = 4;
-constexpr int kGenGramMaxWaves = 8;
 #ifndef YCNR_GEN_GRAM_WAVES_PER_SIMD
 #define YCNR_GEN_GRAM_WAVES_PER_SIMD 2  // one workgroup of eight waves per CU
 #endif
@@ -82,30 +81,6 @@ template <typename T, int V>
 struct alignas(sizeof(T) * V) GenVec {
   T e[V];
 };
-
-// rectangles of sr x cw tiles over a matrix of nb block columns: block rows sr at a time, from the diagonal to the right in steps of cw
-__host__ __device__ constexpr int gen_items(int nb, int sr, int cw) {
-  int n = 0;
-  for (int x = 0; x < nb; x += sr) n += (nb - x + cw - 1) / cw;
-  return n;
-}
-// block rows of a wave's rectangle: float64 tiles take twice the registers, and 2 x 4 tiles leave room for two waves per SIMD
-// of an eight-wave workgroup (k = 256: 20 rectangles, three passes of seven waves; 4 x 4 ran five waves on four SIMDs)
-template <typename T>
-constexpr int gen_rect_rows() { return sizeof(T) == 4 ? 4 : 2; }
-#ifndef YCNR_GEN_SQW_F32
-#define YCNR_GEN_SQW_F32 1  // (2 -- 4 x 8 tiles, three passes of seven waves at k = 512 -- measured slower: 269 against 241 ms per iteration)
-#endif
-template <typename T>
-constexpr int gen_sqw() { return sizeof(T) == 4 ? YCNR_GEN_SQW_F32 : 1; }
-// row pitch of a panel in elements: a multiple of 16, P * sizeof(T) = 64 bytes modulo 256 (float32) / 128 modulo 256 (float64)
-__host__ __device__ constexpr int gen_panel_pitch(int nb, size_t ts) {
-  const int mod = (int)(256 / ts);
-  return nb * 16 + ((16 - (nb * 16) % mod) + mod) % mod;
-}
-template <typename T, int V>
-constexpr int gen_loader_slots() { return V == 1 ? 8 : 4; }
-__host__ __device__ constexpr size_t gen_gram_lds_bytes(int R, int P, size_t ts) { return (size_t)2 * R * ((size_t)P + 1) * ts; }
 
 typedef __bf16 gen_bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned gen_u32x4 __attribute__((ext_vector_type(4)));
@@ -928,13 +903,4 @@ __global__ __launch_bounds__(64 * LW, WPS) void als_gen_solve_left_kernel(GenArg
     a.err->firstRow = sr.row;
   }
 }
-__host__ __device__ constexpr size_t gen_solve_left_lds_bytes(int nb, size_t ts, int pw) {
-  return (2 * 16 * (ts == 8 ? 18 : 20) + 3 * (size_t)nb * 16 + 16 + (size_t)pw * pw * 256) * ts + 64;
-}
-
-__host__ __device__ constexpr size_t gen_solve_lds_bytes(int nb, size_t ts, bool panelLds) {
-  return (2 * 16 * (ts == 8 ? 18 : 20) + 3 * (size_t)nb * 16 + 16 + (panelLds ? (size_t)nb * 256 : 0)) * ts + 64;
-}
-constexpr size_t kGenPanelLdsMax = 36 * 1024;  // panels up to this size live in LDS (k = 512 float32, k = 256 float64: four workgroups per CU)
-
 }  // namespace ycnr

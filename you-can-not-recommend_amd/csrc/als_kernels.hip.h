@@ -25,7 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include <stdint.h>
-#include "schedule.h"
+#include "step_policy.h"
 
 // Register budget of the fused Gramian + solve kernel: 2 waves per SIMD = at most 256
 // registers per lane (k = 100 needs 206 and does not spill; 3 would spill 220 B per lane).
@@ -92,12 +92,10 @@ struct MfmaTraits<double> {
   static __device__ __forceinline__ int cd_row(int lane, int reg) { return (lane >> 4) + (reg << 2); }
 };
 
-__host__ __device__ constexpr int tile_count(int nb) { return nb * (nb + 1) / 2; }
+// tile_count, slab_elems (elements of T one split unit writes): step_policy.h
 __host__ __device__ constexpr int tile_index(int bi, int bj, int nb) {
   return bi * nb - bi * (bi - 1) / 2 + (bj - bi);
 }
-// elements of T one split unit writes: NT tiles x 4 regs x 64 lanes + NB b-partials x 64 lanes
-__host__ __device__ constexpr int64_t slab_elems(int nb) { return (int64_t)(tile_count(nb) * 4 + nb) * 64; }
 
 template <typename T>
 __device__ __forceinline__ T wave_shfl_xor(T v, int mask);
@@ -2101,8 +2099,7 @@ struct GramX6D {
 // zero in the matrix and receive the ratings' planes in LDS -- and a tile of the last block column is A_l, A_m, A_h of its
 // block row against that packed operand (three MFMAs: all nine plane products, as GramX6D's PK3), the corner tile the packed
 // operand against itself (one).  145 MFMAs, 19 DMAs and 38 LDS reads per 32 ratings at k = 100, 19 KB of slots per wave.
-__host__ __device__ constexpr int planes_row_bytes(int nb, bool pack) { return pack ? (nb - 1) * 96 + 32 : nb * 96; }
-__host__ __device__ constexpr bool planes_pack(int k) { return k > 16 && k % 16 == 4; }
+// planes_row_bytes, planes_pack: step_policy.h
 
 // One thread per (row, block, column quad): the exact 3-way split by truncation of GramX6D, columns >= k are zero.
 __global__ void als_split_planes_kernel(const float *__restrict__ fixed, unsigned short *__restrict__ planes, int64_t rows, int k, int nb, int pack) {

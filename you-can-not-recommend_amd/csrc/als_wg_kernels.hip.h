@@ -83,7 +83,7 @@ struct WgCfg {
   // elements of one slab in global memory: the image + b
   static constexpr int64_t SLAB_FLOATS = (int64_t)NT * 256 + NB * 16;
 };
-__host__ __device__ constexpr int64_t wg_slab_floats(int nb) { return (int64_t)tile_count(nb) * 256 + nb * 16; }
+// wg_slab_floats: step_policy.h
 
 // byte offset of a lane's 16 bytes in a tile of the image: element (row r, col c) of the tile lives
 // at float c * 16 + 4 ((r >> 2) ^ ((c >> 1) & 3)) + (r & 3); lane (g, c) owns rows 4g .. 4g+3 of column c

@@ -57,9 +57,7 @@ int fail(int code, const char *fmt, ...) {
                   #expr, hipGetErrorString(e_), __FILE__, __LINE__);                            \
   } while (0)
 
-constexpr int kMaxFactors = 128;     // float64, and the one-wave-per-row float32 kernels
-constexpr int kMaxFactorsBig = 256;  // float32 through the workgroup-per-row kernels of als_wg_kernels.hip.h
-constexpr int kMaxFactorsAny = 4096; // beyond kMaxFactorsBig (float64: kMaxFactors): the any-k path of als_gen_kernels.hip.h
+// kMaxFactors (128), kMaxFactorsBig (256), kMaxFactorsAny (4096) and which path a k takes: step_policy.h
 constexpr int64_t kGenArenaBytes = (int64_t)2 << 30;  // slab arena of the any-k path: rows are solved in batches that fit it
 constexpr int kPairNB = 16;           // block count whose whole rows go Gramian -> slab -> two-wave solve (als_pair_kernels.hip.h): 240 < k <= 256
 constexpr int64_t kPairBatchRows = 4096;   // rows per batch of that path (a slab is 140 KB: 0.57 GB of arena).  One GPU's eighth of C5, ms per
@@ -69,7 +67,6 @@ constexpr int64_t kPairBatchRows = 4096;   // rows per batch of that path (a sla
 constexpr int64_t kBandBytes = (int64_t)96 << 20;  // slice of the fixed matrix one band of chunks gathers from (cache-sized)
 constexpr size_t kErrBytes = 65536;
 constexpr size_t kZeroRowBytes = 32768 + 64;  // >= kMaxFactorsAny doubles: the "row" the dual kernels gather for ratings past a row's end
-constexpr int kMaxDualBlocksSmallK = 5;  // k <= 128: beyond 80 ratings the row kernel (k x k) is cheaper (MAL scale, k = 100: 6 -> 5 blocks took 0.2 ms off the user half-step once the solve had lost its readlanes and transposes; 4 was slower)
 
 size_t tsize(int dtype) { return dtype == YCNR_F64 ? 8 : 4; }
 
@@ -91,10 +88,6 @@ struct Ratings {
   }
 };
 
-
-// the any-k path (als_gen_kernels.hip.h): float32 beyond 256 factors, float64 beyond 128
-bool is_gen(int dtype, int k) { return k > (dtype == YCNR_F32 ? kMaxFactorsBig : kMaxFactors); }
-
 // A piece's plan (schedule.h) on the device: the counters of the plan, and the owner of the lists' device copies and the slabs
 struct Schedule : PlanCounts {
   std::vector<GenBatch> genBatches;
@@ -104,6 +97,7 @@ struct Schedule : PlanCounts {
   float *dRowSlabs = nullptr;  // k > 240: the images of a batch of whole rows between their Gramian and their two-wave solve
   int64_t rowSlabRows = 0;
   int64_t nUnits = 0, nSplit = 0;
+  int dualMax = 0;  // dual_max_ratings as the plan was built with it (YCNR_DUAL_MAX_BLOCKS is read per upload)
   void release() {
     if (dUnits) (void)hipFree(dUnits);
     if (dSplit) (void)hipFree(dSplit);
@@ -113,17 +107,35 @@ struct Schedule : PlanCounts {
   }
 };
 
-// environment toggles for A/B experiments from unmodified hosts, read once per process
-struct EnvFlags {
-  bool noDualX6, noX6d, noFusedX6d, noOverlap, ignoreNumeric, noDualQuad, noGraph, noPair, g32, noPk3;
+// environment toggles for A/B experiments from unmodified hosts, read once per process; the ones step_policy.h decides by
+// are its Toggles (all but YCNR_DUAL_MAX_BLOCKS, which is read per upload: upload_toggles)
+struct EnvFlags : Toggles {
+  bool noDualX6, noX6d, noFusedX6d, ignoreNumeric, noDualQuad, noPair, g32, noPk3;
   size_t k1LdsPad;
 };
 const EnvFlags &env_flags() {
-  static const EnvFlags f = {getenv("YCNR_NO_DUAL_X6") != nullptr, getenv("YCNR_NO_X6D") != nullptr, getenv("YCNR_NO_FUSED_X6D") != nullptr,
-                             getenv("YCNR_NO_OVERLAP") != nullptr, getenv("YCNR_IGNORE_NUMERIC") != nullptr, getenv("YCNR_NO_DUAL_QUAD") != nullptr,
-                             getenv("YCNR_NO_GRAPH") != nullptr, getenv("YCNR_NO_PAIR") != nullptr, getenv("YCNR_G32") != nullptr, getenv("YCNR_NO_PK3") != nullptr,
-                             getenv("YCNR_K1_LDSPAD") ? (size_t)atoi(getenv("YCNR_K1_LDSPAD")) : 0};
+  static const EnvFlags f = [] {
+    EnvFlags e{};
+    e.noOverlap = getenv("YCNR_NO_OVERLAP") != nullptr, e.noGraph = getenv("YCNR_NO_GRAPH") != nullptr, e.noX6p = getenv("YCNR_NO_X6P") != nullptr;
+    e.genRightLooking = getenv("YCNR_GEN_RIGHT_LOOKING") != nullptr, e.noGenX6 = getenv("YCNR_NO_GEN_X6") != nullptr;
+    e.noDualX6 = getenv("YCNR_NO_DUAL_X6") != nullptr, e.noX6d = getenv("YCNR_NO_X6D") != nullptr, e.noFusedX6d = getenv("YCNR_NO_FUSED_X6D") != nullptr;
+    e.ignoreNumeric = getenv("YCNR_IGNORE_NUMERIC") != nullptr, e.noDualQuad = getenv("YCNR_NO_DUAL_QUAD") != nullptr;
+    e.noPair = getenv("YCNR_NO_PAIR") != nullptr, e.g32 = getenv("YCNR_G32") != nullptr, e.noPk3 = getenv("YCNR_NO_PK3") != nullptr;
+    e.k1LdsPad = getenv("YCNR_K1_LDSPAD") ? (size_t)atoi(getenv("YCNR_K1_LDSPAD")) : 0;
+    return e;
+  }();
   return f;
+}
+// the toggles of an upload: YCNR_DUAL_MAX_BLOCKS as it is now (experiments set it between uploads)
+Toggles upload_toggles() {
+  Toggles t = env_flags();
+  if (const char *e = getenv("YCNR_DUAL_MAX_BLOCKS")) t.dualMaxBlocks = std::max(0, atoi(e));
+  return t;
+}
+// bytes of the slab arena of the any-k path (YCNR_GEN_ARENA_MB, read per upload and per out-of-place call: tests force several batches)
+int64_t gen_arena_bytes() {
+  if (const char *e = getenv("YCNR_GEN_ARENA_MB")) return (int64_t)std::max(1, atoi(e)) << 20;
+  return kGenArenaBytes;
 }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize, set once per (kernel, device, size) instead of per half-step
@@ -165,10 +177,6 @@ int side_streams() {
   }();
   return n;
 }
-constexpr int64_t kGraphMaxRatings = 2 * 1024 * 1024;  // uploads below this replay their half-step as a captured hipGraph ...
-constexpr int64_t kGraphMinRatings = 256 * 1024;       // ... unless they are so small that the graph launch itself costs more than four
-                                                        // kernel launches (ML-100k shape: 0.124 ms per iteration launch by launch, 0.174 as graphs)
-constexpr int64_t kMinOverlapDualRows = 1024;  // fewer dual-form rows than this: everything in stream order
 
 struct DualPlan {
   bool noX6 = false;     // YCNR_FLAG_NO_BF16X6: float32-MFMA Gramian in the dual kernels too
@@ -236,6 +244,14 @@ int launch_duals(const StepArgs<T> &args, const DualPlan &dp, hipStream_t stream
     return launch_duals<T, M - 1>(args, dp, stream);
   }
   return YCNR_OK;
+}
+
+// the dual classes on `stream` itself, one after the other, whatever side streams the plan has
+template <typename T>
+int launch_duals_in_order(const StepArgs<T> &args, const DualPlan &dp, hipStream_t stream) {
+  DualPlan serial = dp;
+  serial.nSide = 0;
+  return launch_duals<T>(args, serial, stream);
 }
 
 // The dual classes next to the row kernel: the side streams wait for dp.fork (which the caller has recorded), take the classes
@@ -472,12 +488,8 @@ int launch_wg_nb(StepArgs<float> args, int64_t nSplitUnits, int64_t nPrimal, int
     HIP_TRY(hipGetLastError());
   }
   if (ev) HIP_TRY(hipEventRecord(ev[2], stream));
-  if (dp.nPrimal >= 0 && !sideDuals) {  // (YCNR_FLAG_NO_OVERLAP, or too few rows to pay for the fork and the joins)
-    DualPlan serial = dp;
-    serial.nSide = 0;
-    int rc = launch_duals<float>(args, serial, stream);
-    if (rc) return rc;
-  }
+  if (dp.nPrimal >= 0 && !sideDuals)  // (YCNR_FLAG_NO_OVERLAP, or too few rows to pay for the fork and the joins)
+    if (int rc = launch_duals_in_order<float>(args, dp, stream)) return rc;
   if (sideDuals)
     if (int rc = join_duals(dp, stream)) return rc;
   if (ev) HIP_TRY(hipEventRecord(ev[3], stream));
@@ -503,75 +515,43 @@ int launch_step_big(const StepArgs<float> &args, int64_t nUnits, int64_t nSplitU
 // (float32: rows of at most 176 ratings, whose n x n form does not depend on k)
 template <typename T>
 int launch_step_gen(const StepArgs<T> &args, const std::vector<GenBatch> &batches, hipStream_t stream, hipEvent_t *ev, const DualPlan &dp) {
-  GenArgs<T> ga{args, (args.k + 15) / 16, 0, 0, 0};
-  const bool panelLds = (size_t)ga.nb * 256 * sizeof(T) <= kGenPanelLdsMax;
-  const size_t lds = gen_solve_lds_bytes(ga.nb, sizeof(T), panelLds);
-  if (lds > 160 * 1024) return fail(YCNR_ERR_UNSUPPORTED, "factorsCount %d: the right-hand side does not fit a CU's LDS", args.k);
-  const void *solveFn = panelLds ? reinterpret_cast<const void *>(als_gen_solve_kernel<T, true>) : reinterpret_cast<const void *>(als_gen_solve_kernel<T, false>);
-  if (int rc = set_max_lds(solveFn, lds)) return rc;
-  // the left-looking solve where a block of four rows fits the registers of eight waves: float32 up to k = 512, float64 up to 256 (beyond: the right-looking kernel)
-  // (YCNR_GEN_RIGHT_LOOKING: the right-looking kernel everywhere, for A/B runs)
-  static const bool rightOnly = getenv("YCNR_GEN_RIGHT_LOOKING") != nullptr;
+  const GenChoice c = choose_gen(sizeof(T), args.k, (reinterpret_cast<uintptr_t>(args.fixed) & 15) == 0, env_flags());
+  if (c.status == kGenRhsTooLarge) return fail(YCNR_ERR_UNSUPPORTED, "factorsCount %d: the right-hand side does not fit a CU's LDS", args.k);
+  if (c.status == kGenPanelTooLarge) return fail(YCNR_ERR_UNSUPPORTED, "factorsCount %d: a panel of four ratings does not fit a CU's LDS", args.k);
+  GenArgs<T> ga{args, c.nb, 0, 0, 0};
+  const void *solveFn = c.panelLds ? reinterpret_cast<const void *>(als_gen_solve_kernel<T, true>) : reinterpret_cast<const void *>(als_gen_solve_kernel<T, false>);
+  if (int rc = set_max_lds(solveFn, c.solveLds)) return rc;
   const void *leftFn = nullptr;
-  int leftWaves = 8, leftPw = 4;
-  if (!rightOnly) {
-    if constexpr (sizeof(T) == 4) {
-      const int maxc = (ga.nb + 7) / 8;
-      leftFn = maxc <= 2 ? reinterpret_cast<const void *>(als_gen_solve_left_kernel<T, 2, 4, 8, true, 2>)
-               : maxc <= 4 ? reinterpret_cast<const void *>(als_gen_solve_left_kernel<T, 4, 4, 8, true, 2>) : nullptr;
-    } else if (ga.nb <= 16) {
-      // (k = 256, 200 K x 20 K, per iteration: right-looking 301 ms; 4 rows x 8 waves as in float32, one workgroup per CU: 347;
-      // 2 rows x 8 waves, two per CU: 277; 2 rows x 4 waves, three per CU: 253)
+  if (c.left) {
+    if constexpr (sizeof(T) == 4)
+      leftFn = c.leftMaxc == 2 ? reinterpret_cast<const void *>(als_gen_solve_left_kernel<T, 2, 4, 8, true, 2>) : reinterpret_cast<const void *>(als_gen_solve_left_kernel<T, 4, 4, 8, true, 2>);
+    else
       leftFn = reinterpret_cast<const void *>(als_gen_solve_left_kernel<T, 4, 2, 4, false, 3>);
-      leftWaves = 4, leftPw = 2;
-    }
+    if (int rc = set_max_lds(leftFn, c.leftLds)) return rc;
   }
-  const size_t leftLds = gen_solve_left_lds_bytes(ga.nb, sizeof(T), leftPw);
-  if (leftFn)
-    if (int rc = set_max_lds(leftFn, leftLds)) return rc;
-  // Gramian: 16-byte loads when every row of the fixed matrix starts on a 16-byte boundary, single elements otherwise;
-  // the waves of a workgroup share the rectangles of a pass evenly; R ratings per panel: as many as two buffers of <= 72 KB
-  // (two workgroups per CU) and the loader's slots allow, at least 4
   constexpr int V = 16 / (int)sizeof(T);
-  const bool vec = args.k % V == 0 && (reinterpret_cast<uintptr_t>(args.fixed) & 15) == 0;
-  const int nSq = gen_items(ga.nb, gen_rect_rows<T>(), gen_sqw<T>() * kGenSq), passes = (nSq + kGenGramMaxWaves - 1) / kGenGramMaxWaves;
-  const int waves = std::max(2, (nSq + passes - 1) / passes), nthr = 64 * waves;
-  const int P = gen_panel_pitch(ga.nb, sizeof(T));
-  int slots = vec ? gen_loader_slots<T, V>() : gen_loader_slots<T, 1>();
-  int R = 32;
-  // float32 with 16-byte rows whose panel of 32 ratings fits one workgroup's LDS AND its loader slots (8 per thread of at most
-  // eight waves: 32 (k / 4) <= 8 * 512, i.e. k <= 512): the products on the bf16 pipe (X6); 516 <= k keeps float32 MFMAs
-  static const bool noGenX6 = getenv("YCNR_NO_GEN_X6") != nullptr;  // (A/B runs)
-  const bool x6 = sizeof(T) == 4 && vec && !noGenX6 && gen_gram_lds_bytes(32, P, sizeof(T)) <= 150 * 1024 &&
-                  (int64_t)32 * (args.k / V) <= (int64_t)8 * nthr;
-  if (x6) slots = 8;
-  else
-    while (R > 4 && (gen_gram_lds_bytes(R, P, sizeof(T)) > 72 * 1024 || (int64_t)R * (args.k / (vec ? V : 1)) > (int64_t)slots * nthr)) R >>= 1;
-  const size_t gramLds = gen_gram_lds_bytes(R, P, sizeof(T));
-  if (gramLds > 150 * 1024 || (int64_t)R * (args.k / (vec ? V : 1)) > (int64_t)slots * nthr)
-    return fail(YCNR_ERR_UNSUPPORTED, "factorsCount %d: a panel of four ratings does not fit a CU's LDS", args.k);
-  const void *gramFn = vec ? reinterpret_cast<const void *>(als_gen_gram_kernel<T, V>) : reinterpret_cast<const void *>(als_gen_gram_kernel<T, 1>);
+  const void *gramFn = c.vec ? reinterpret_cast<const void *>(als_gen_gram_kernel<T, V>) : reinterpret_cast<const void *>(als_gen_gram_kernel<T, 1>);
   if constexpr (sizeof(T) == 4)
-    if (x6) gramFn = reinterpret_cast<const void *>(als_gen_gram_kernel<T, V, true>);
-  if (int rc = set_max_lds(gramFn, gramLds)) return rc;
+    if (c.x6) gramFn = reinterpret_cast<const void *>(als_gen_gram_kernel<T, V, true>);
+  if (int rc = set_max_lds(gramFn, c.gramLds)) return rc;
   if (ev) HIP_TRY(hipEventRecord(ev[0], stream));
   for (const GenBatch &b : batches) {
     ga.slabBase = b.slabBase;
     ga.firstUnit = b.slabBase;  // units of split rows are numbered like their slabs
     ga.firstSplit = b.firstSplit;
     {
-      int Rv = R, Pv = P;
+      int Rv = c.R, Pv = c.P;
       void *gargs[] = {(void *)&ga, (void *)&Rv, (void *)&Pv};
-      HIP_TRY(hipLaunchKernel(gramFn, dim3((unsigned)b.nSlabs), dim3(nthr), gargs, gramLds, stream));
+      HIP_TRY(hipLaunchKernel(gramFn, dim3((unsigned)b.nSlabs), dim3(c.threads), gargs, c.gramLds, stream));
     }
     HIP_TRY(hipGetLastError());
     if (leftFn) {
       void *kargs[] = {(void *)&ga};
-      HIP_TRY(hipLaunchKernel(leftFn, dim3((unsigned)b.nSplit), dim3(64 * leftWaves), kargs, leftLds, stream));
-    } else if (panelLds) {
-      hipLaunchKernelGGL((als_gen_solve_kernel<T, true>), dim3((unsigned)b.nSplit), dim3(kGenThreads), lds, stream, ga);
+      HIP_TRY(hipLaunchKernel(leftFn, dim3((unsigned)b.nSplit), dim3(64 * c.leftWaves), kargs, c.leftLds, stream));
+    } else if (c.panelLds) {
+      hipLaunchKernelGGL((als_gen_solve_kernel<T, true>), dim3((unsigned)b.nSplit), dim3(kGenThreads), c.solveLds, stream, ga);
     } else {
-      hipLaunchKernelGGL((als_gen_solve_kernel<T, false>), dim3((unsigned)b.nSplit), dim3(kGenThreads), lds, stream, ga);
+      hipLaunchKernelGGL((als_gen_solve_kernel<T, false>), dim3((unsigned)b.nSplit), dim3(kGenThreads), c.solveLds, stream, ga);
     }
     HIP_TRY(hipGetLastError());
   }
@@ -581,12 +561,9 @@ int launch_step_gen(const StepArgs<T> &args, const std::vector<GenBatch> &batche
   }
   if constexpr (std::is_same<T, float>::value) {
     if (dp.nPrimal >= 0) {
-      DualPlan serial = dp;
-      serial.nSide = 0;
       StepArgs<float> a2 = args;
       a2.firstFused = 0;
-      int rc = launch_duals<float>(a2, serial, stream);
-      if (rc) return rc;
+      if (int rc = launch_duals_in_order<float>(a2, dp, stream)) return rc;
     }
   }
   if (ev) {
@@ -606,54 +583,15 @@ int launch_step(const StepArgs<T> &args, int64_t nUnits, int64_t nSplitUnits, in
   return launch_rows<T>(rk, args, nUnits, nSplitUnits, nSplit, stream, ev, dp);
 }
 
-int slab_nb(int k) { return (k + 15) / 16; }
-
-// float32, k = 16 m + 4 (m >= 1), k <= 128: the last 4 columns of the Gramian go to the VALU
-bool use_valu_edge(const ycnr_als_options &o) {
-  return o.dtype == YCNR_F32 && !(o.flags & YCNR_FLAG_NO_VALU_EDGE) && o.factorsCount >= 20 && o.factorsCount <= kMaxFactors &&
-         o.factorsCount % 16 == 4;
-}
-
-// split chunks on the bf16 matrix pipe (exact 3-way split, six products): float32, one-wave
-// kernels, fixed matrix addressable by a 32-bit buffer offset
-bool use_slab_x6(const ycnr_als_options &o, int side) {
-  const int64_t fixedRows = side == YCNR_BY_USER ? o.totalItemsCount : o.totalUsersCount;
-  return o.dtype == YCNR_F32 && !(o.flags & YCNR_FLAG_NO_BF16X6) && o.factorsCount <= kMaxFactors &&
-         fixedRows * o.factorsCount * 4 < ((int64_t)1 << 31);
-}
-
-// The fused row kernel on pre-split planes (GramX6P): float32 bf16x6 path, k % 4 == 0, k <= 124 with a padded column for
-// the right-hand side (k % 16 != 0), and a plane matrix (96 bytes per 16-column block and row) that stays cache-resident.
-constexpr int64_t kPlanesMaxBytes = (int64_t)64 << 20;
-bool use_planes(const ycnr_als_options &o, int side) {
-  static const bool off = getenv("YCNR_NO_X6P") != nullptr;
-  const int64_t fixedRows = side == YCNR_BY_USER ? o.totalItemsCount : o.totalUsersCount;
-  const int k = o.factorsCount;
-  return !off && use_slab_x6(o, side) && !(o.flags & YCNR_FLAG_LDS_SOLVER) && k % 4 == 0 && k <= 124 && k % 16 != 0 &&
-         fixedRows * planes_row_bytes(slab_nb(k), planes_pack(k)) <= kPlanesMaxBytes;
-}
-
-// registers (x 64 lanes x sizeof(T)) one split unit writes
-int64_t slab_regs(const ycnr_als_options &o, int side) {
-  const int nb = slab_nb(o.factorsCount);
-  if (use_valu_edge(o) && !use_slab_x6(o, side)) {
-    const int nbm = nb - 1;
-    return tile_count(nbm) * 4 + nbm + nbm * 4 + 8;
-  }
-  return tile_count(nb) * 4 + nb;
-}
-
-// Longest row solved in dual form (0 = never): float32 MFMA solver only, rows of 16-byte
-// multiples, and strictly fewer 16-blocks than the primal form would use.
-int dual_max_ratings(const ycnr_als_options &o) {
-  // (k > 128 with k % 4 != 0 runs on rows padded to a multiple of 4: see kPad)
-  if (o.dtype != YCNR_F32 || (o.flags & (YCNR_FLAG_LDS_SOLVER | YCNR_FLAG_NO_DUAL)) || (o.factorsCount % 4 != 0 && o.factorsCount <= kMaxFactors)) return 0;
-  const int nb = slab_nb(o.factorsCount);
-  // k > 128: every row that is not dual goes through slabs and the 4-wave LDS solve, whose cost
-  // grows with k^3; an n x n problem with n <= 176 still fits one wave's registers
-  int most = o.factorsCount > kMaxFactors ? kMaxDualBlocks : kMaxDualBlocksSmallK;
-  if (const char *e = getenv("YCNR_DUAL_MAX_BLOCKS")) most = std::max(0, std::min(atoi(e), o.factorsCount > kMaxFactors ? kMaxDualBlocks : kMaxDualBlocksSmallK));  // experiments
-  return 16 * std::min(most, nb - 1);
+// A plan of out_of_place_plan_params (fold-in beyond 128 factors, the level-1 portion op) on its path: every row in primal
+// form, no timing events, everything on `stream`
+template <typename T>
+int launch_out_of_place(const StepArgs<T> &a, const PiecePlan &plan, hipStream_t stream) {
+  const PathKind path = step_path(std::is_same<T, double>::value, a.k);
+  if (path == kAnyK) return launch_step_gen<T>(a, plan.genBatches, stream, nullptr, DualPlan());
+  if constexpr (std::is_same<T, float>::value)
+    if (path == kWorkgroup) return launch_step_big(a, (int64_t)plan.units.size(), plan.nSlabs, (int64_t)plan.split.size(), stream, nullptr, DualPlan());
+  return launch_step<T>(a, (int64_t)plan.units.size(), plan.nSlabs, (int64_t)plan.split.size(), stream, nullptr);
 }
 
 // copy `bytes` from src (host or device) to a device destination
@@ -900,6 +838,8 @@ struct ycnr_als {
 
   int64_t rows(int side) const { return side == YCNR_BY_USER ? opt.totalUsersCount : opt.totalItemsCount; }
   size_t ts() const { return tsize(opt.dtype); }
+  // what step_policy.h decides by for a half-step of `side`: the options as the kernels see them (copt)
+  StepShape shape(int side) const { return StepShape{copt.dtype == YCNR_F64, copt.factorsCount, (uint32_t)copt.flags, rows(1 - side)}; }
 };
 
 // the kernels' arguments for one piece of a side: its schedule and ratings, the two factor matrices (or their padded copies)
@@ -908,7 +848,7 @@ static StepArgs<T> step_args(const ycnr_als *h, int side, const Part &part, cons
   const double lambda = side == YCNR_BY_USER ? h->copt.userFactReg : h->copt.itemFactReg;
   return StepArgs<T>{part.S.dUnits, part.S.dSplit, part.R.dIndx, (const T *)part.R.dVals, (const T *)fixed, (const T *)h->dZeros, (T *)solved,
                      (T *)part.S.dSlabs, h->dErr, lambda, h->copt.factorsCount, 0, 0,
-                     use_slab_x6(h->copt, side) ? (uint32_t)(h->rows(1 - side) * h->copt.factorsCount * 4) : 0u};
+                     use_slab_x6(h->shape(side)) ? (uint32_t)(h->rows(1 - side) * h->copt.factorsCount * 4) : 0u};
 }
 
 extern "C" {
@@ -1489,41 +1429,21 @@ static int upload_ratings(ycnr_als *h, Ratings &R, int64_t totalRows, int64_t op
   return YCNR_OK;
 }
 
-// slabs the arena of the any-k path holds: rows are solved in batches that fit it (a k = 512 float32 image is 541 KB and
-// several MB beyond 1024 factors: a portion of 10 K short rows would ask for gigabytes)
-static int64_t gen_arena_slabs(size_t slabBytes) {
-  int64_t arenaBytes = kGenArenaBytes;
-  if (const char *e = getenv("YCNR_GEN_ARENA_MB")) arenaBytes = (int64_t)std::max(1, atoi(e)) << 20;  // tests force several batches
-  return std::max<int64_t>(1, arenaBytes / (int64_t)slabBytes);
-}
-
 // Upload + schedule (schedule.h) of one piece [rowBegin, rowEnd) of a side's rows into newR / S (both released
 // by the caller when this fails).
 static int build_part(ycnr_als *h, int side, const int64_t *rowPtr, const int32_t *indx, const void *vals, int64_t rowBegin,
-                      int64_t rowEnd, int memKind, Ratings &newR, Schedule &S, int64_t sideNnz, int64_t sideSplitNnz) {
+                      int64_t rowEnd, int memKind, Ratings &newR, Schedule &S, SideNnz sideNnz) {
   std::vector<int64_t> hp;
   int rc = upload_ratings(h, newR, h->rows(side), h->rows(1 - side), rowPtr, indx, vals, rowBegin,
                           rowEnd, memKind, hp, side == YCNR_BY_USER ? "set_ratings(byUser)" : "set_ratings(byItem)");
   if (rc) return rc;
-  const bool gen = is_gen(h->copt.dtype, h->copt.factorsCount);  // any-k path: every primal row through slabs, in row order
-  const bool big = !gen && h->copt.factorsCount > kMaxFactors;
-  const size_t slabElems = gen ? (size_t)gen_slab_elems(slab_nb(h->copt.factorsCount))
-                               : big ? (size_t)wg_slab_floats(slab_nb(h->copt.factorsCount)) : (size_t)slab_regs(h->copt, side) * 64;
-  PlanParams P;
-  P.kind = gen ? kAnyK : big ? kWorkgroup : kOneWave;
-  // k > 128: a unit is a whole workgroup's work, so chunks are long (a slab is 140 KB at k = 256)
-  // (an explicit options.chunkRatings is honoured there too: tests cut short rows into chunks with it)
-  // The automatic chunk length follows the split rows of the WHOLE side (sideNnz: their ratings), not of this piece: where a
-  // split row is cut decides the order its partial sums are added in, so a length that depended on the piece would make the
-  // factors depend on how the rows are cut into shards and pieces (and a feedback re-cut would change them: round-3 review).
-  P.chunk = h->autoChunk ? (gen ? kGenChunk : big ? kWgChunk : auto_chunk(sideNnz, sideSplitNnz)) : h->copt.chunkRatings;
-  P.fusedMax = big && h->autoChunk ? kWgFusedMax : std::min(P.chunk, h->copt.chunkRatings);
-  P.maxSlabs = big ? kMaxSlabsPerRowBig : kMaxSlabsPerRow;
-  P.dualMax = dual_max_ratings(h->copt);
-  P.k = h->opt.factorsCount;
+  const StepShape shape = h->shape(side);
+  const size_t slabElems = (size_t)resident_slab_elems(shape);
   static const int order = getenv("YCNR_ROW_ORDER") ? atoi(getenv("YCNR_ROW_ORDER")) : -1;  // 0: whole rows stay sorted (A/B)
-  P.shuffle = order < 0;
-  if (gen) P.arenaSlabs = gen_arena_slabs(slabElems * h->ts());
+  const PlanParams P = resident_plan_params(shape, upload_toggles(), h->opt.factorsCount, h->autoChunk, h->copt.chunkRatings, sideNnz, order < 0,
+                                            gen_arena_bytes());
+  const bool big = P.kind == kWorkgroup;
+  S.dualMax = P.dualMax;
   PiecePlan plan = plan_piece(hp.data(), rowBegin, rowEnd - rowBegin, P);
   // Band-major chunks (schedule.h), unless YCNR_FLAG_NO_BANDS: when the fixed matrix is far larger than the last-level
   // cache, in bands of kBandBytes of it
@@ -1602,7 +1522,7 @@ static int set_ratings_parts(ycnr_als *h, int side, const int64_t *rowPtr, const
     Part &p = pend.parts[(size_t)i];
     hipError_t e = p.create_events();
     if (e != hipSuccess) return fail(YCNR_ERR_HIP, "set_ratings: hipEventCreate: %s", hipGetErrorString(e));
-    int rc = build_part(h, side, rowPtr, indx, vals, b[i], b[i + 1], memKind, p.R, p.S, sideNnz.nnz, sideNnz.splitNnz);
+    int rc = build_part(h, side, rowPtr, indx, vals, b[i], b[i + 1], memKind, p.R, p.S, sideNnz);
     if (rc) return rc;
   }
   HIP_TRY(hipStreamSynchronize(h->stream));  // nothing in flight still reads the previous upload
@@ -1764,7 +1684,7 @@ int ycnr_als_set_ratings_banded(ycnr_als *h, int side, const int64_t *rowPtr, co
     B.rank = rank;
     B.rankBands.assign(rankBands, rankBands + world + 1);
     B.ownerBounds.assign(ownerBounds, ownerBounds + world + 1);
-    B.slabElems = (int64_t)slab_regs(h->copt, side) * 64;
+    B.slabElems = slab_regs(h->shape(side)) * 64;
     BandedPlan plan = plan_banded(hp.data(), counts.data(), nBands, rankBands, ownerBounds, rank, world, chunk, B.slabElems);
     if (plan.error) return fail(YCNR_ERR_UNSUPPORTED, "set_ratings_banded: %s", plan.error);
     static_cast<BandedLayout &>(B) = plan;
@@ -1909,25 +1829,27 @@ static int launch_part(ycnr_als *h, int side, Part &part, hipStream_t stream, bo
   const Ratings &R = part.R;
   const Schedule &S = part.S;
   hipEvent_t *ev = branches ? nullptr : part.ev;
+  const StepShape shape = h->shape(side);
+  const PathKind path = step_path(shape.f64, shape.k);
   if (h->copt.dtype == YCNR_F32) {
     // (copt.factorsCount = kPad when the matrices are padded)
     StepArgs<float> a = h->kPad ? step_args<float>(h, side, part, h->padded[1 - side], h->padded[side])
                                 : step_args<float>(h, side, part, h->factors[1 - side], h->factors[side]);
     if (h->kPad) a.kReal = h->opt.factorsCount;
-    if (h->planes[1 - side] && h->planesValid[1 - side] && use_planes(h->copt, side)) {
+    if (h->planes[1 - side] && h->planesValid[1 - side] && use_planes(shape, env_flags())) {
       a.planes = h->planes[1 - side];
       a.planesBytes = (uint32_t)(h->rows(1 - side) * planes_row_bytes(slab_nb(h->copt.factorsCount), planes_pack(h->copt.factorsCount)));
     }
     DualPlan dp;
     dp.noX6 = (h->copt.flags & YCNR_FLAG_NO_BF16X6) != 0;
     dp.fewSlabs = S.maxRowSlabs <= kFewSlabs;
-    if (dual_max_ratings(h->copt) > 0) {
+    if (S.dualMax > 0) {
       dp.nPrimal = S.nPrimal;
       dp.first = S.dualFirst;
       dp.count = S.dualCount;
       // (the fork and join cost nine more runtime calls per half-step: with a few hundred rows,
       // where the half-step is bound by the launches themselves, they made it slower)
-      if ((S.dualRows >= kMinOverlapDualRows || (branches && S.dualRows > 0)) && !inOrder && !(h->copt.flags & YCNR_FLAG_NO_OVERLAP) && !env_flags().noOverlap) {
+      if (duals_on_side_streams(shape, env_flags(), S.dualRows, branches, inOrder)) {
         // (a captured small half-step keeps two branches for its dual classes: every branch is a join, 30 - 60 us each)
         dp.nSide = branches ? std::min(2, side_streams()) : side_streams();
         for (int i = 0; i < dp.nSide; ++i) {
@@ -1943,12 +1865,13 @@ static int launch_part(ycnr_als *h, int side, Part &part, hipStream_t stream, bo
       dp.slabJoin = part.slabJoin;
     }
     int rc;
-    if (h->copt.factorsCount > kMaxFactors)
-      rc = is_gen(YCNR_F32, h->copt.factorsCount) ? launch_step_gen<float>(a, S.genBatches, stream, ev, dp)
-                                                  : launch_step_big(a, S.nUnits, S.nSlabs, S.nSplit, stream, ev, dp, S.dRowSlabs, S.rowSlabRows);
+    if (path == kAnyK)
+      rc = launch_step_gen<float>(a, S.genBatches, stream, ev, dp);
+    else if (path == kWorkgroup)
+      rc = launch_step_big(a, S.nUnits, S.nSlabs, S.nSplit, stream, ev, dp, S.dRowSlabs, S.rowSlabRows);
     else
       rc = launch_step<float>(a, S.nUnits, S.nSlabs, S.nSplit, stream, ev, (h->copt.flags & YCNR_FLAG_LDS_SOLVER) != 0, dp,
-                              use_valu_edge(h->copt), use_slab_x6(h->copt, side));
+                              use_valu_edge(shape), use_slab_x6(shape));
     if (rc || !h->kPad) return rc;
     // the piece's solved rows back into the caller's matrix (before its exchange)
     const int64_t nr = R.rowEnd - R.rowBegin, n = nr * h->opt.factorsCount;
@@ -1960,7 +1883,7 @@ static int launch_part(ycnr_als *h, int side, Part &part, hipStream_t stream, bo
     return YCNR_OK;
   }
   const StepArgs<double> a = step_args<double>(h, side, part, h->factors[1 - side], h->factors[side]);
-  if (is_gen(YCNR_F64, h->copt.factorsCount)) return launch_step_gen<double>(a, S.genBatches, stream, ev, DualPlan());
+  if (path == kAnyK) return launch_step_gen<double>(a, S.genBatches, stream, ev, DualPlan());
   DualPlan dpd;  // float64 has no dual classes; the chunk branch of the small-upload form applies
   dpd.fork = part.fork;
   if (branches) {
@@ -1989,7 +1912,6 @@ static void note_enqueued(ycnr_als *h, int side, const std::vector<Part> &parts)
   h->info.struct_size = (int32_t)sizeof(ycnr_als_step_info);
   h->info.side = side;
   h->info.parts = (int32_t)parts.size();
-  const bool dual = h->opt.dtype == YCNR_F32 && dual_max_ratings(h->copt) > 0;
   for (const Part &p : parts) {
     const Schedule &S = p.S;
     h->info.rows += S.solvedRows;
@@ -1998,13 +1920,12 @@ static void note_enqueued(ycnr_als *h, int side, const std::vector<Part> &parts)
     h->info.splitRows += S.nSplit;
     h->info.fusedRows += S.solvedRows - S.nSplit;
     h->info.fusedRatings += S.fusedRatings;
-    if (dual) {
+    if (S.dualMax > 0) {
       h->info.dualRows += S.dualRows;
       h->info.dualRatings += S.dualRatings;
       h->info.dualFlops += S.dualFlops;
-      if (S.dualRows >= kMinOverlapDualRows && !is_gen(YCNR_F32, h->copt.factorsCount) && !(h->opt.flags & YCNR_FLAG_NO_OVERLAP) &&
-          !env_flags().noOverlap)
-        h->info.dualOverlapped = 1;
+      // (not told whether the piece ran in order, as one of several in flight: DESIGN.md section 8)
+      if (duals_on_side_streams(h->shape(side), env_flags(), S.dualRows, false, false)) h->info.dualOverlapped = 1;
     }
   }
   h->infoPending = true;
@@ -2045,7 +1966,7 @@ static int step_banded_t(ycnr_als *h, int side) {
   const StepArgs<T> a = step_args<T>(h, side, part, h->factors[1 - side], h->factors[side]);
   // the chunk kernel and the band reduce of this k (no row kernel, no dual classes)
   RowKernels<T> rk;
-  if (int rc = row_kernels<T>(a, (h->copt.flags & YCNR_FLAG_LDS_SOLVER) != 0, use_valu_edge(h->copt), use_slab_x6(h->copt, side), false, rk)) return rc;
+  if (int rc = row_kernels<T>(a, (h->copt.flags & YCNR_FLAG_LDS_SOLVER) != 0, use_valu_edge(h->shape(side)), use_slab_x6(h->shape(side)), false, rk)) return rc;
   if (int rc = set_max_lds(reinterpret_cast<const void *>(rk.band), rk.ldsReduce)) return rc;
   HIP_TRY(hipEventRecord(part.ev[0], stream));
   const int bpr = (int)(B.rankBands[(size_t)B.rank + 1] - B.rankBands[(size_t)B.rank]);
@@ -2224,7 +2145,7 @@ int ycnr_als_step_async(ycnr_als *h, int side) {
   // (not for uploads below kGraphMinRatings, whose half-step is a handful of launches: one more launch costs what the planes save)
   int64_t sideRatings = 0;
   for (const Part &p : parts) sideRatings += p.R.nnz;
-  const bool planesNow = use_planes(h->copt, side) && sideRatings >= kGraphMinRatings;
+  const bool planesNow = use_planes(h->shape(side), env_flags()) && sideRatings >= kGraphMinRatings;
   if (!planesNow) h->planesValid[1 - side] = false;
   auto split_planes = [&]() -> int {
     if (!planesNow) return YCNR_OK;
@@ -2246,9 +2167,7 @@ int ycnr_als_step_async(ycnr_als *h, int side) {
   {
     ycnr_als::GraphSlot &gs = h->graph[side];
     // (a padded upload -- kPad -- is captured too: the pads above are plain launches in front of the graph, the unpad of the piece's rows is part of it)
-    const bool graphable = !exchange && parts.size() == 1 && h->copt.factorsCount <= kMaxFactors &&
-                           parts[0].R.nnz < kGraphMaxRatings && parts[0].R.nnz >= kGraphMinRatings && h->stream == h->ownStream &&
-                           !(h->opt.flags & (YCNR_FLAG_NO_OVERLAP | YCNR_FLAG_NO_GRAPH)) && !env_flags().noOverlap && !env_flags().noGraph;
+    const bool graphable = ycnr::graphable(h->shape(side), env_flags(), exchange, parts.size(), parts[0].R.nnz, h->stream == h->ownStream);
     if (graphable && gs.state == 1) {
       for (int i = 0; i < side_streams(); ++i)  // (not inside the capture)
         if (!h->sideStream[i]) HIP_TRY(hipStreamCreateWithFlags(&h->sideStream[i], hipStreamNonBlocking));
@@ -2707,18 +2626,9 @@ int fold_check(const char *what, const ycnr_als *h, int side, int64_t nRows, con
 template <typename T>
 int fold_launch_steps(ycnr_als *h, int side, int64_t nRows, const int64_t *rowPtr, double lambda) {
   typedef ycnr_als A;
-  const int k = h->opt.factorsCount, dtype = h->opt.dtype;
-  const bool gen = is_gen(dtype, k) || k % 4 != 0;  // (float32 rows that are not 16-byte multiples: the any-k path, as in level 1)
-  const bool big = !gen;
-  const int nb = slab_nb(k);
-  const size_t slabElems = gen ? (size_t)gen_slab_elems(nb) : (size_t)wg_slab_floats(nb);
-  PlanParams P;
-  P.kind = gen ? kAnyK : kWorkgroup;
-  P.chunk = gen ? kGenChunk : kWgChunk;
-  P.fusedMax = big ? kWgFusedMax : 0;
-  P.k = k;
-  P.shuffle = P.sortSplit = false;
-  if (gen) P.arenaSlabs = gen_arena_slabs(slabElems * sizeof(T));
+  const int k = h->opt.factorsCount;
+  const PlanParams P = out_of_place_plan_params(std::is_same<T, double>::value, k, gen_arena_bytes());
+  const size_t slabElems = (size_t)step_slab_elems(P.kind, k);
   h->foldPlan = plan_piece(rowPtr, 0, nRows, P);  // (kept on the handle: its lists are the source of the copies below)
   const PiecePlan &plan = h->foldPlan;
   if (int rc = rec_reserve(h->rec[A::FOLD_UNITS], sizeof(Unit) * std::max<size_t>(1, plan.units.size()))) return rc;
@@ -2733,10 +2643,7 @@ int fold_launch_steps(ycnr_als *h, int side, int64_t nRows, const int64_t *rowPt
   StepArgs<T> a{(const Unit *)h->rec[A::FOLD_UNITS].p, (const SplitRow *)h->rec[A::FOLD_SPLIT].p, (const int32_t *)h->rec[A::FOLD_INDX].p,
                 (const T *)h->rec[A::FOLD_VALS].p, (const T *)h->factors[1 - side], (const T *)h->dZeros, (T *)h->rec[A::FOLD_ROWS].p,
                 (T *)h->rec[A::FOLD_SLABS].p, (ErrInfo *)h->rec[A::FOLD_ERR].p, lambda, k, 0, 0, 0u};
-  if (gen) return launch_step_gen<T>(a, plan.genBatches, h->stream, nullptr, DualPlan());
-  if constexpr (std::is_same<T, float>::value)
-    return launch_step_big(a, (int64_t)plan.units.size(), plan.nSlabs, (int64_t)plan.split.size(), h->stream, nullptr, DualPlan());
-  return fail(YCNR_ERR_UNSUPPORTED, "fold-in: no kernel for factorsCount %d", k);
+  return launch_out_of_place<T>(a, plan, h->stream);
 }
 
 // Uploads the (validated) request and enqueues its solve on the handle's stream; records recEv[0] in front of the kernels.
@@ -3123,9 +3030,6 @@ int64_t als_calc_portion(double lambda, int k, const int32_t *alsRows, const int
     return fail(YCNR_ERR_INVALID, "AlsCalcPortion: null argument");
   if (k < 1) return fail(YCNR_ERR_INVALID, "AlsCalcPortion: k < 1");
   if (k > kMaxFactorsAny) return fail(YCNR_ERR_UNSUPPORTED, "factorsCount %d > %d is not supported by this build", k, kMaxFactorsAny);
-  // the any-k path also takes float32 rows that are not 16-byte multiples above 128 factors (the resident trainer pads those)
-  const bool gen = is_gen(dtype, k) || (k > kMaxFactors && k % 4 != 0);
-  const bool big = !gen && k > kMaxFactors;
   if (!(lambda >= 0)) return fail(YCNR_ERR_INVALID, "AlsCalcPortion: negative lambda");
   const int nRows = alsRows[0];
   if (nRows < 0) return fail(YCNR_ERR_INVALID, "AlsCalcPortion: alsRows[0] < 0");
@@ -3175,21 +3079,13 @@ int64_t als_calc_portion(double lambda, int k, const int32_t *alsRows, const int
       uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
     }
   }
-  const int nb = slab_nb(k);
-  const size_t slabElems = gen ? (size_t)gen_slab_elems(nb) : big ? (size_t)wg_slab_floats(nb) : (size_t)slab_elems(nb);
   // the plan of a piece of the resident trainer (build_part) with every row in primal form and the split rows in row order;
   // any-k path: solved in batches whose images fit the arena
-  PlanParams P;
-  P.kind = gen ? kAnyK : big ? kWorkgroup : kOneWave;
-  P.chunk = gen ? kGenChunk : big ? kWgChunk : kDefaultChunk;
-  P.fusedMax = big ? kWgFusedMax : 0;
-  P.k = k;
-  P.shuffle = P.sortSplit = false;
-  if (gen) P.arenaSlabs = gen_arena_slabs(slabElems * sizeof(T));
+  const PlanParams P = out_of_place_plan_params(std::is_same<T, double>::value, k, gen_arena_bytes());
+  const size_t slabElems = (size_t)step_slab_elems(P.kind, k);
   const PiecePlan plan = plan_piece(rowPtr.data(), 0, nRows, P);
   const std::vector<Unit> &units = plan.units;
   const std::vector<SplitRow> &split = plan.split;
-  const int64_t nSlabs = plan.nSlabs;
 #define L1_TRY(expr)                                                                                  \
   do {                                                                                                \
     hipError_t e_ = (expr);                                                                           \
@@ -3235,15 +3131,7 @@ int64_t als_calc_portion(double lambda, int k, const int32_t *alsRows, const int
     const T *dFixed = pinned ? (const T *)C.pinned.p : (const T *)(db + oFixed);
     StepArgs<T> a{(const Unit *)(db + oUnits), (const SplitRow *)(db + oSplit), (const int32_t *)(db + oIndx), (const T *)(db + oVals), dFixed, dZeros,
                   (T *)(db + oSolved), (T *)C.slabs.p, dErr, lambda, k, 0, 0, 0u};
-    if (gen) {
-      rc = launch_step_gen<T>(a, plan.genBatches, stream, nullptr, DualPlan());
-    } else if constexpr (std::is_same<T, float>::value) {
-      if (big) rc = launch_step_big(a, (int64_t)units.size(), nSlabs, (int64_t)split.size(), stream, nullptr, DualPlan());
-      else rc = launch_step<T>(a, (int64_t)units.size(), nSlabs, (int64_t)split.size(), stream, nullptr);
-    } else {
-      rc = launch_step<T>(a, (int64_t)units.size(), nSlabs, (int64_t)split.size(), stream, nullptr);
-    }
-    if (rc) return rc;
+    if ((rc = launch_out_of_place<T>(a, plan, stream))) return rc;
   }
   // rows without ratings are never written by the kernels and never copied back below
   L1_TRY(hipMemcpyAsync(hb + oSolved, db + oSolved, oErr + sizeof(ErrInfo), hipMemcpyDeviceToHost, stream));
