@@ -725,6 +725,61 @@ def test_errors_are_reported_not_fatal(als):
     dev.destroy()
 
 
+@pytest.mark.parametrize("dt", [np.float32, np.float64])
+def test_handle_lifecycle_uploads_replace_and_bound_memory_survives(als, dt):
+    """Who owns what over a handle's life: a failed upload leaves the previous one intact, a new upload replaces the old one
+    cleanly (its graph slots included), destroy() does not free a matrix the caller bound, and a handle that never saw an
+    upload goes away quietly.  Everything is compared bit for bit with the first run from the same start."""
+    import torch
+    from ycnr_als import YcnrError, _lib
+    k, users, items = 8, 40, 30
+    bu, bi, U, V = make_problem(users, items, k, density=0.3, seed=301, dtype=dt)
+    bu2, bi2, _, _ = make_problem(users, items, k, density=0.3, seed=302, dtype=dt)
+    dev = als.AlsDevice(k, users, items, useDoublePrecision=(dt == np.float64))
+
+    def upload(byUser, byItem):
+        dev.set_ratings("byUser", byUser.rowPtr, byUser.indx, byUser.vals)
+        dev.set_ratings("byItem", byItem.rowPtr, byItem.indx, byItem.vals)
+
+    def iteration():  # from (U, V): the user rows after their half-step, the item rows after theirs
+        dev.set_factors("byUser", U)
+        dev.set_factors("byItem", V)
+        assert dev.step("byUser").numericErrors == 0
+        uHalf = dev.get_factors("byUser")
+        assert dev.step("byItem").numericErrors == 0
+        return uHalf, dev.get_factors("byItem")
+
+    # 1. the first run
+    upload(bu, bi)
+    U1, V1 = iteration()
+    assert not np.array_equal(U1, U) and not np.array_equal(V1, V)
+    # 2. a failed upload (column id == items) leaves the previous upload intact
+    bad = bu.indx.copy()
+    bad[len(bad) // 2] = items
+    with pytest.raises(YcnrError) as e:
+        dev.set_ratings("byUser", bu.rowPtr, bad, bu.vals)
+    assert e.value.code == _lib.ERR_INVALID
+    U2, V2 = iteration()
+    assert np.array_equal(U2, U1) and np.array_equal(V2, V1)
+    # 3. another problem of the same shape replaces it, then the first one replaces that
+    upload(bu2, bi2)
+    U3, V3 = iteration()
+    assert not np.array_equal(U3, U1)
+    upload(bu, bi)
+    U4, V4 = iteration()
+    assert np.array_equal(U4, U1) and np.array_equal(V4, V1)
+    # 4. a matrix of the caller's, bound: solved in place, and still the caller's after destroy()
+    mine = torch.from_numpy(U).to("cuda")
+    dev.set_factors("byItem", V)
+    dev.bind_factors("byUser", mine)
+    assert dev.step("byUser").numericErrors == 0
+    dev.destroy()
+    torch.cuda.synchronize()
+    assert np.array_equal(mine.cpu().numpy(), U1)
+    # 5. a handle that never had an upload
+    als.AlsDevice(k, users, items, useDoublePrecision=(dt == np.float64)).destroy()
+
+
 @pytest.mark.parametrize("double", [True, False], ids=["f64", "f32"])
 def test_full_iterations_ml100k_shape(als, oracle, double):
     """C1 shape (943 x 1682, ~100k ratings, k = 20): 3 full ALS iterations through the host

@@ -7,6 +7,7 @@
 #include "../../include/ycnr_als.h"
 #include "als_kernels.hip.h"
 #include "kernel_choice.h"
+#include "owned.h"
 #include "als_wg_kernels.hip.h"
 #include "als_pair_kernels.hip.h"
 #ifdef YCNR_WITH_G32  // devtest build only (make EXTRA=-DYCNR_WITH_G32): the 32 x 32 Gramian kernel of round 3, measured equal
@@ -70,41 +71,68 @@ constexpr size_t kZeroRowBytes = 32768 + 64;  // >= kMaxFactorsAny doubles: the 
 
 size_t tsize(int dtype) { return dtype == YCNR_F64 ? 8 : 4; }
 
+// Who frees what (owned.h): every device buffer, page-locked host buffer, event and stream of this file is a member or a local
+// of one of these types, and these deleters are the only calls that free one.  Kernel arguments and the other views
+// (DualPlan, StepArgs, RmseArgs) stay raw and are filled from get().
+struct FreeDev {
+  void operator()(void *p) const { (void)hipFree(p); }
+};
+struct FreeHost {
+  void operator()(void *p) const { (void)hipHostFree(p); }
+};
+struct FreeEvent {
+  void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); }
+};
+struct FreeStream {  // what is still queued on the stream may read buffers that are freed next
+  void operator()(hipStream_t s) const {
+    (void)hipStreamSynchronize(s);
+    (void)hipStreamDestroy(s);
+  }
+};
+template <typename T>
+using DevPtr = Owned<T *, FreeDev>;
+template <typename T>
+using HostPtr = Owned<T *, FreeHost>;
+using Event = Owned<hipEvent_t, FreeEvent>;
+using Stream = Owned<hipStream_t, FreeStream>;
+
+// The grow-only buffers (GrowBuf): level-1 device arenas, their page-locked host image, the per-call buffers of recommend / fold-in
+struct DevAlloc {
+  static hipError_t alloc(size_t n, void **p) { return hipMalloc(p, n); }
+  static void free(void *p) { FreeDev{}(p); }
+};
+struct ArenaAlloc : DevAlloc {
+  static size_t grow(size_t bytes) { return std::max<size_t>(bytes + bytes / 2, 4096); }
+};
+struct ExactAlloc : DevAlloc {
+  static size_t grow(size_t bytes) { return bytes; }
+};
+struct PinnedAlloc {
+  static hipError_t alloc(size_t n, void **p) { return hipHostMalloc(p, n, hipHostMallocDefault); }
+  static void free(void *p) { FreeHost{}(p); }
+  static size_t grow(size_t bytes) { return bytes + bytes / 2; }
+};
+
+hipError_t new_event(Event &e, bool timing) { return timing ? hipEventCreate(e.put()) : hipEventCreateWithFlags(e.put(), hipEventDisableTiming); }
+
 struct Ratings {
   int64_t rowBegin = 0, rowEnd = 0, nnz = 0;
-  int64_t *dRowPtr = nullptr;  // local, rebased to 0 (RMSE only)
-  int32_t *dIndx = nullptr;
-  void *dVals = nullptr;
+  DevPtr<int64_t> dRowPtr;  // local, rebased to 0 (RMSE only)
+  DevPtr<int32_t> dIndx;
+  DevPtr<void> dVals;
   bool loaded = false;
-  void release() {
-    if (dRowPtr) (void)hipFree(dRowPtr);
-    if (dIndx) (void)hipFree(dIndx);
-    if (dVals) (void)hipFree(dVals);
-    dRowPtr = nullptr;
-    dIndx = nullptr;
-    dVals = nullptr;
-    loaded = false;
-    nnz = 0;
-  }
 };
 
 // A piece's plan (schedule.h) on the device: the counters of the plan, and the owner of the lists' device copies and the slabs
 struct Schedule : PlanCounts {
   std::vector<GenBatch> genBatches;
-  Unit *dUnits = nullptr;
-  SplitRow *dSplit = nullptr;
-  void *dSlabs = nullptr;
-  float *dRowSlabs = nullptr;  // k > 240: the images of a batch of whole rows between their Gramian and their two-wave solve
+  DevPtr<Unit> dUnits;
+  DevPtr<SplitRow> dSplit;
+  DevPtr<void> dSlabs;
+  DevPtr<float> dRowSlabs;  // k > 240: the images of a batch of whole rows between their Gramian and their two-wave solve
   int64_t rowSlabRows = 0;
   int64_t nUnits = 0, nSplit = 0;
   int dualMax = 0;  // dual_max_ratings as the plan was built with it (YCNR_DUAL_MAX_BLOCKS is read per upload)
-  void release() {
-    if (dUnits) (void)hipFree(dUnits);
-    if (dSplit) (void)hipFree(dSplit);
-    if (dSlabs) (void)hipFree(dSlabs);
-    if (dRowSlabs) (void)hipFree(dRowSlabs);
-    *this = Schedule();
-  }
 };
 
 // environment toggles for A/B experiments from unmodified hosts, read once per process; the ones step_policy.h decides by
@@ -602,7 +630,6 @@ int copy_in(void *dst, const void *src, size_t bytes, int memKind, hipStream_t s
   return YCNR_OK;
 }
 
-// out[i] = dSrc[pos[i]] for a host list of positions (one small gather kernel + two copies)
 // out[q] = first position p in [beg[q], end[q]) with indx[p] >= key[q] (end[q] if none); rows sorted by column id
 __global__ void lower_bound_i32_kernel(const int32_t *indx, const int64_t *beg, const int64_t *end, const int32_t *key,
                                        int64_t *out, int64_t n) {
@@ -623,40 +650,32 @@ int lower_bound_i32(const int32_t *dIndx, const std::vector<int64_t> &beg, const
   const size_t n = key.size();
   out.resize(n);
   if (n == 0) return YCNR_OK;
-  char *d = nullptr;
-  HIP_TRY(hipMalloc(&d, n * 28));
-  int64_t *dBeg = (int64_t *)d, *dEnd = dBeg + n, *dOut = dEnd + n;
+  DevPtr<char> d;
+  HIP_TRY(hipMalloc(d.put(), n * 28));
+  int64_t *dBeg = (int64_t *)d.get(), *dEnd = dBeg + n, *dOut = dEnd + n;
   int32_t *dKey = (int32_t *)(dOut + n);
-  hipError_t e = hipMemcpyAsync(dBeg, beg.data(), n * 8, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(dEnd, end.data(), n * 8, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(dKey, key.data(), n * 4, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(lower_bound_i32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, dIndx, dBeg, dEnd, dKey, dOut, (int64_t)n);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(out.data(), dOut, n * 8, hipMemcpyDeviceToHost, stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  (void)hipFree(d);
-  if (e != hipSuccess) return fail(YCNR_ERR_HIP, "lower_bound_i32: %s", hipGetErrorString(e));
+  HIP_TRY(hipMemcpyAsync(dBeg, beg.data(), n * 8, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(dEnd, end.data(), n * 8, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(dKey, key.data(), n * 4, hipMemcpyHostToDevice, stream));
+  hipLaunchKernelGGL(lower_bound_i32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, dIndx, dBeg, dEnd, dKey, dOut, (int64_t)n);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out.data(), dOut, n * 8, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
   return YCNR_OK;
 }
 
 // got = {max, min} of the n > 0 column ids on the device
 int index_max_min(const int32_t *dIndx, int64_t n, hipStream_t stream, int32_t got[2]) {
-  int32_t *dmm = nullptr;
-  HIP_TRY(hipMalloc(&dmm, 2 * sizeof(int32_t)));
-  int32_t init[2] = {INT32_MIN, INT32_MAX};
-  hipError_t e = hipMemcpyAsync(dmm, init, sizeof init, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess) {
-    const int blocks = (int)std::min<int64_t>(2048, (n + 255) / 256);
-    hipLaunchKernelGGL(max_i32_kernel, dim3(blocks), dim3(256), 0, stream, dIndx, n, dmm, dmm + 1);
-    e = hipGetLastError();
-  }
   got[0] = got[1] = 0;
-  if (e == hipSuccess) e = hipMemcpyAsync(got, dmm, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  (void)hipFree(dmm);
-  if (e != hipSuccess) return fail(YCNR_ERR_HIP, "index range check failed: %s", hipGetErrorString(e));
+  DevPtr<int32_t> dmm;
+  HIP_TRY(hipMalloc(dmm.put(), 2 * sizeof(int32_t)));
+  const int32_t init[2] = {INT32_MIN, INT32_MAX};
+  HIP_TRY(hipMemcpyAsync(dmm.get(), init, sizeof init, hipMemcpyHostToDevice, stream));
+  const int blocks = (int)std::min<int64_t>(2048, (n + 255) / 256);
+  hipLaunchKernelGGL(max_i32_kernel, dim3(blocks), dim3(256), 0, stream, dIndx, n, dmm.get(), dmm.get() + 1);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(got, dmm.get(), 2 * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
   return YCNR_OK;
 }
 
@@ -690,40 +709,21 @@ int check_index_bounds(const int32_t *dIndx, int64_t n, int64_t lo, int64_t hi, 
 struct Part {
   Ratings R;
   Schedule S;
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t ready = nullptr, x0 = nullptr, x1 = nullptr;
+  Event ev[5], ready, x0, x1;
   // fork / join of the piece's dual-class launches on the handle's side streams, and "all kernels of the piece done":
   // per piece, because two pieces are in flight at a time (on the handle's two piece streams)
-  hipEvent_t fork = nullptr, join[kSideStreams] = {}, done = nullptr, slabJoin = nullptr;
-  hipError_t create_events() {
+  Event fork, join[kSideStreams], done, slabJoin;
+  hipError_t create_events() {  // (only the parts of an upload get events: a Part is also a plain value)
     hipError_t e = hipSuccess;
-    for (int i = 0; i < 5 && e == hipSuccess; ++i) e = hipEventCreate(&ev[i]);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&fork, hipEventDisableTiming);
-    for (int i = 0; i < kSideStreams && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&join[i], hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&slabJoin, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ready, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreate(&x0);
-    if (e == hipSuccess) e = hipEventCreate(&x1);
+    for (int i = 0; i < 5 && e == hipSuccess; ++i) e = new_event(ev[i], true);
+    if (e == hipSuccess) e = new_event(fork, false);
+    for (int i = 0; i < kSideStreams && e == hipSuccess; ++i) e = new_event(join[i], false);
+    if (e == hipSuccess) e = new_event(done, false);
+    if (e == hipSuccess) e = new_event(slabJoin, false);
+    if (e == hipSuccess) e = new_event(ready, false);
+    if (e == hipSuccess) e = new_event(x0, true);
+    if (e == hipSuccess) e = new_event(x1, true);
     return e;
-  }
-  void release() {
-    R.release();
-    S.release();
-    for (int i = 0; i < 5; ++i)
-      if (ev[i]) (void)hipEventDestroy(ev[i]);
-    if (ready) (void)hipEventDestroy(ready);
-    if (x0) (void)hipEventDestroy(x0);
-    if (x1) (void)hipEventDestroy(x1);
-    if (fork) (void)hipEventDestroy(fork);
-    if (done) (void)hipEventDestroy(done);
-    if (slabJoin) (void)hipEventDestroy(slabJoin);
-    for (int i = 0; i < kSideStreams; ++i) {
-      if (join[i]) (void)hipEventDestroy(join[i]);
-      join[i] = nullptr;
-    }
-    for (int i = 0; i < 5; ++i) ev[i] = nullptr;
-    ready = x0 = x1 = fork = done = slabJoin = nullptr;
   }
 };
 
@@ -733,42 +733,29 @@ struct BandedSide : BandedLayout {
   bool on = false;
   int nBands = 0, world = 1, rank = 0;
   std::vector<int64_t> rankBands, ownerBounds;    // world + 1 band indices / row ids
-  SlabSum *dSums = nullptr;
-  void *dRecv = nullptr;
-  const void **dTable = nullptr;                   // owned rows x nBands slab pointers (null: no rating of the row in that band)
+  DevPtr<SlabSum> dSums;
+  DevPtr<void> dRecv;
+  DevPtr<const void *> dTable;                     // owned rows x nBands slab pointers (null: no rating of the row in that band)
   int64_t recvSlabs = 0, ownedSolved = 0, nSums = 0;
   int64_t slabElems = 0;
-  hipEvent_t evRecv = nullptr, evStage[kFewSlabs] = {};  // stage s: the group computed in it is complete (on its piece stream)
-  void release() {
-    if (dSums) (void)hipFree(dSums);
-    if (dRecv) (void)hipFree(dRecv);
-    if (dTable) (void)hipFree(dTable);
-    if (evRecv) (void)hipEventDestroy(evRecv);
-    for (hipEvent_t &e : evStage) {
-      if (e) (void)hipEventDestroy(e);
-      e = nullptr;
-    }
-    dSums = nullptr;
-    dRecv = nullptr;
-    dTable = nullptr;
-    evRecv = nullptr;
-    on = false;
-  }
+  Event evRecv, evStage[kFewSlabs];  // stage s: the group computed in it is complete (on its piece stream)
 };
 
 }  // namespace
 
 struct ycnr_als {
   ycnr_als_options opt{};
-  hipStream_t ownStream = nullptr;
-  hipStream_t stream = nullptr;
-  hipStream_t sideStream[kSideStreams] = {};  // dual classes next to the row kernel (DualPlan)
+  // The streams stand in front of every buffer and event: members are destroyed in reverse order of declaration, so the
+  // streams outlive everything their work may touch (ycnr_als_destroy: side streams, piece streams, the handle's own last).
+  Stream ownStream;
   // A sharded side is solved in pieces (the exchange of one travels while the next is solved).  The pieces are
   // independent (different rows of the solved matrix), so they alternate over two streams that fork from and join the
   // step's stream: the kernels of piece c + 1 fill the tails of piece c's (one GPU's eighth of the MAL-scale user side,
   // 4 pieces in stream order: 2.5 ms against 2.0 ms in one piece).
-  hipStream_t pieceStream[2] = {};
-  hipEvent_t evStepStart = nullptr;
+  Stream pieceStream[2];
+  Stream sideStream[kSideStreams];  // dual classes next to the row kernel (DualPlan)
+  hipStream_t stream = nullptr;     // the one half-steps run on: ownStream.get() or the caller's (ycnr_als_set_stream)
+  Event evStepStart;
   // Small uploads: the launches of a half-step captured once and replayed (hipGraph).  state: 0 = not run yet (the
   // first half-step runs launch by launch: it sets function attributes), 1 = capture at the next one, 2 = exec is
   // valid, -1 = capture failed once, stay with launches.  Dropped whenever something a kernel argument points
@@ -785,45 +772,41 @@ struct ycnr_als {
       g.state = 0;
     }
   }
-  void *factors[2] = {nullptr, nullptr};
-  bool ownFactors[2] = {false, false};
+  void *factors[2] = {nullptr, nullptr};  // what the kernels and ycnr_als_factors_ptr read: the handle's own matrix or a bound one
+  DevPtr<void> factorsMem[2];             // the handle's own (empty once the caller has bound theirs: ycnr_als_bind_factors)
   // GramX6P: the fixed matrix of a half-step split into bf16 planes once (als_split_planes_kernel), where it is small
   // enough to stay cache-resident (the user half-step: the item matrix); planes[s] belongs to factors[s]
-  unsigned short *planes[2] = {nullptr, nullptr};
+  DevPtr<unsigned short> planes[2];
   bool planesValid[2] = {false, false};  // the half-step in flight split factors[s] into planes[s]
   int kPad = 0;                          // != 0: float32, factorsCount % 4 != 0: the kernels work on copies padded to a multiple of 4
   ycnr_als_options copt{};               // opt as the kernels see it: factorsCount = kPad when padded (schedules, kernel choice, slab sizes)
-  float *padded[2] = {nullptr, nullptr};  // [rows x kPad] copies the kernels of that case work on
+  DevPtr<float> padded[2];               // [rows x kPad] copies the kernels of that case work on
   bool autoChunk = false;  // options.chunkRatings was 0: sized per upload (auto_chunk)
   std::vector<Part> parts[2];      // the side's local row shard, cut into pipelined pieces (usually one)
   BandedSide banded[2];            // ycnr_als_set_ratings_banded: the side's half-step is sharded by bands of columns
   bool deferExchange[2] = {false, false};  // ycnr_als_defer_exchange: the side's half-steps leave the solved rows where they are
   std::vector<int64_t> bounds[2];   // sharded upload: row bounds of every rank's pieces, world x (nParts + 1)
   Comm comm;                        // exchange step of the multi-GPU path (comm_impl.hip.h)
-  hipEvent_t evComputeEnd = nullptr;
+  Event evComputeEnd;
   bool exchangedInStep = false;
   Ratings rmse[2];
   double lastRmseMs = -1.0;  // device time of the last ycnr_als_rmse (its kernel, HIP events on the handle's stream)
   // ycnr_als_recommend: its device buffers grow on demand and stay (a second call of the same size allocates nothing)
-  struct RecBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-  };
   enum { REC_USER_IDS, REC_SKIP_PTR, REC_SKIP, REC_PART_V, REC_PART_I, REC_IDS, REC_PRED, REC_CNT, REC_ROWS, REC_SCORES,
          // ycnr_als_fold_in / ycnr_als_recommend_for_ratings: the request's CSR, the solved rows and their status, the ids to store at;
          // factorsCount > 128: the plan of the step kernels (units, split rows, slabs) and their error record
          FOLD_PTR, FOLD_INDX, FOLD_VALS, FOLD_ROWS, FOLD_STATUS, FOLD_STORE, FOLD_UNITS, FOLD_SPLIT, FOLD_SLABS, FOLD_ERR, FOLD_PAD, REC_NBUF };
-  RecBuf rec[REC_NBUF];
-  hipEvent_t recEv[2] = {nullptr, nullptr};
+  GrowBuf<ExactAlloc> rec[REC_NBUF];
+  Event recEv[2];
   PiecePlan foldPlan;  // ycnr_als_fold_in beyond 128 factors: the plan whose lists are being copied to the device
-  ErrInfo *dErr = nullptr;
+  DevPtr<ErrInfo> dErr;
   // The error record is never reset on the device: its count only grows, the host remembers what it has seen
   // (errSeen) and gets the record through an 8-byte copy into page-locked memory at the end of every half-step
   // (before: a memset kernel in front of every half-step and a synchronous copy behind it -- 30 us of a 90 us
   // half-step at the ML-100k shape).
-  ErrInfo *hErr = nullptr;
+  HostPtr<ErrInfo> hErr;
   int32_t errSeen = 0;
-  void *dZeros = nullptr;  // the zero "factor row" read for ratings past a unit's end
+  DevPtr<void> dZeros;  // the zero "factor row" read for ratings past a unit's end
   ycnr_als_step_info info{};  // of the half-step being enqueued / completed
   bool infoPending = false;   // some half-step has been enqueued and not completed by ycnr_als_sync
   int infoSide = 0;           // side of the last half-step enqueued
@@ -846,8 +829,8 @@ struct ycnr_als {
 template <typename T>
 static StepArgs<T> step_args(const ycnr_als *h, int side, const Part &part, const void *fixed, void *solved) {
   const double lambda = side == YCNR_BY_USER ? h->copt.userFactReg : h->copt.itemFactReg;
-  return StepArgs<T>{part.S.dUnits, part.S.dSplit, part.R.dIndx, (const T *)part.R.dVals, (const T *)fixed, (const T *)h->dZeros, (T *)solved,
-                     (T *)part.S.dSlabs, h->dErr, lambda, h->copt.factorsCount, 0, 0,
+  return StepArgs<T>{part.S.dUnits.get(), part.S.dSplit.get(), part.R.dIndx.get(), (const T *)part.R.dVals.get(), (const T *)fixed, (const T *)h->dZeros.get(), (T *)solved,
+                     (T *)part.S.dSlabs.get(), h->dErr.get(), lambda, h->copt.factorsCount, 0, 0,
                      use_slab_x6(h->shape(side)) ? (uint32_t)(h->rows(1 - side) * h->copt.factorsCount * 4) : 0u};
 }
 
@@ -866,24 +849,6 @@ int ycnr_device_count(void) {
 
 // ---- N1: split + stats (prep_kernels.hip.h) ----
 namespace {
-struct DevBuf {
-  void *p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-};
-// a pair of timing events that is destroyed on every return path
-struct EvPair {
-  hipEvent_t a = nullptr, b = nullptr;
-  hipError_t create() {
-    hipError_t e = hipEventCreate(&a);
-    return e == hipSuccess ? hipEventCreate(&b) : e;
-  }
-  ~EvPair() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-};
 int timed(hipEvent_t e0, hipEvent_t e1, double *ms) {
   HIP_TRY(hipEventRecord(e1, nullptr));
   HIP_TRY(hipEventSynchronize(e1));
@@ -909,14 +874,15 @@ int ycnr_split_to_sets(int64_t rows, const int64_t *rowPtr, int8_t *types, const
     if (rowPtr[r + 1] - rowPtr[r] >= ((int64_t)1 << 31)) return fail(YCNR_ERR_UNSUPPORTED, "row %lld too long", (long long)r);
   }
   if (nnz == 0) return YCNR_OK;
-  DevBuf dPtr, dTypes;
-  HIP_TRY(hipMalloc(&dPtr.p, (size_t)(rows + 1) * 8));
-  HIP_TRY(hipMalloc(&dTypes.p, (size_t)nnz));
-  HIP_TRY(hipMemcpy(dPtr.p, rowPtr, (size_t)(rows + 1) * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dTypes.p, types, (size_t)nnz, hipMemcpyHostToDevice));
-  EvPair evp;
-  HIP_TRY(evp.create());
-  const hipEvent_t e0 = evp.a, e1 = evp.b;
+  DevPtr<void> dPtr, dTypes;
+  HIP_TRY(hipMalloc(dPtr.put(), (size_t)(rows + 1) * 8));
+  HIP_TRY(hipMalloc(dTypes.put(), (size_t)nnz));
+  HIP_TRY(hipMemcpy(dPtr.get(), rowPtr, (size_t)(rows + 1) * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dTypes.get(), types, (size_t)nnz, hipMemcpyHostToDevice));
+  Event ev0, ev1;
+  HIP_TRY(hipEventCreate(ev0.put()));
+  HIP_TRY(hipEventCreate(ev1.put()));
+  const hipEvent_t e0 = ev0.get(), e1 = ev1.get();
   HIP_TRY(hipEventRecord(e0, nullptr));
   // three classes of rows: up to kSplitRankRow ratings one wave ranks every rating (O(n^2 / 64), cheapest for short rows);
   // longer ones find the two thresholds by bisection instead -- one wave up to kSplitShortRow ratings, a 1024-thread
@@ -930,28 +896,28 @@ int ycnr_split_to_sets(int64_t rows, const int64_t *rowPtr, int8_t *types, const
   for (int q = 1; q < 3; ++q)
     std::stable_sort(lists[q].begin(), lists[q].end(),
                      [&](int32_t x, int32_t y) { return rowPtr[x + 1] - rowPtr[x] > rowPtr[y + 1] - rowPtr[y]; });
-  DevBuf dList[3];
+  DevPtr<void> dList[3];
   for (int q = 0; q < 3; ++q) {
     if (lists[q].empty()) continue;
-    HIP_TRY(hipMalloc(&dList[q].p, lists[q].size() * 4));
-    HIP_TRY(hipMemcpy(dList[q].p, lists[q].data(), lists[q].size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMalloc(dList[q].put(), lists[q].size() * 4));
+    HIP_TRY(hipMemcpy(dList[q].get(), lists[q].data(), lists[q].size() * 4, hipMemcpyHostToDevice));
   }
   HIP_TRY(hipEventRecord(e0, nullptr));  // the kernels only (lists are part of the upload)
   if (!lists[1].empty())
-    hipLaunchKernelGGL((split_to_sets_select_kernel<kSplitLdsKeys, 1024>), dim3((unsigned)lists[1].size()), dim3(1024), 0, nullptr, (const int64_t *)dPtr.p,
-                       (const int32_t *)dList[1].p, (int64_t)lists[1].size(), (int8_t *)dTypes.p, (int)pcts[0], (int)pcts[1], seed);
+    hipLaunchKernelGGL((split_to_sets_select_kernel<kSplitLdsKeys, 1024>), dim3((unsigned)lists[1].size()), dim3(1024), 0, nullptr, (const int64_t *)dPtr.get(),
+                       (const int32_t *)dList[1].get(), (int64_t)lists[1].size(), (int8_t *)dTypes.get(), (int)pcts[0], (int)pcts[1], seed);
   if (!lists[2].empty())
     hipLaunchKernelGGL((split_to_sets_select_kernel<kSplitShortRow, 64>), dim3((unsigned)std::min<size_t>(lists[2].size(), (size_t)1 << 20)), dim3(64), 0,
-                       nullptr, (const int64_t *)dPtr.p, (const int32_t *)dList[2].p, (int64_t)lists[2].size(), (int8_t *)dTypes.p,
+                       nullptr, (const int64_t *)dPtr.get(), (const int32_t *)dList[2].get(), (int64_t)lists[2].size(), (int8_t *)dTypes.get(),
                        (int)pcts[0], (int)pcts[1], seed);
   if (!lists[0].empty())
     hipLaunchKernelGGL((split_to_sets_kernel<kSplitRankRow, 64>), dim3((unsigned)std::min<size_t>(lists[0].size(), (size_t)1 << 20)), dim3(64), 0,
-                       nullptr, (const int64_t *)dPtr.p, (const int32_t *)dList[0].p, (int64_t)lists[0].size(), (int8_t *)dTypes.p,
+                       nullptr, (const int64_t *)dPtr.get(), (const int32_t *)dList[0].get(), (int64_t)lists[0].size(), (int8_t *)dTypes.get(),
                        (int)pcts[0], (int)pcts[1], seed);
   hipError_t le = hipGetLastError();
   int rc = le == hipSuccess ? timed(e0, e1, deviceMs) : fail(YCNR_ERR_HIP, "split_to_sets launch: %s", hipGetErrorString(le));
   if (rc) return rc;
-  HIP_TRY(hipMemcpy(types, dTypes.p, (size_t)nnz, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(types, dTypes.get(), (size_t)nnz, hipMemcpyDeviceToHost));
   return YCNR_OK;
 }
 
@@ -964,20 +930,21 @@ int ycnr_rating_stats(int dtype, int64_t rows, const int64_t *rowPtr, const void
   const int64_t nnz = rowPtr[rows];
   if (nnz < 0 || (nnz > 0 && !vals)) return fail(YCNR_ERR_INVALID, "ycnr_rating_stats: bad nnz / null vals");
   const size_t ts = tsize(dtype);
-  DevBuf dPtr, dVals, dTypes, dCnt, dSum;
-  HIP_TRY(hipMalloc(&dPtr.p, (size_t)(rows + 1) * 8));
-  HIP_TRY(hipMalloc(&dVals.p, std::max<size_t>((size_t)nnz * ts, 8)));
-  HIP_TRY(hipMalloc(&dCnt.p, (size_t)rows * 4));
-  HIP_TRY(hipMalloc(&dSum.p, (size_t)rows * 8));
-  HIP_TRY(hipMemcpy(dPtr.p, rowPtr, (size_t)(rows + 1) * 8, hipMemcpyHostToDevice));
-  if (nnz) HIP_TRY(hipMemcpy(dVals.p, vals, (size_t)nnz * ts, hipMemcpyHostToDevice));
+  DevPtr<void> dPtr, dVals, dTypes, dCnt, dSum;
+  HIP_TRY(hipMalloc(dPtr.put(), (size_t)(rows + 1) * 8));
+  HIP_TRY(hipMalloc(dVals.put(), std::max<size_t>((size_t)nnz * ts, 8)));
+  HIP_TRY(hipMalloc(dCnt.put(), (size_t)rows * 4));
+  HIP_TRY(hipMalloc(dSum.put(), (size_t)rows * 8));
+  HIP_TRY(hipMemcpy(dPtr.get(), rowPtr, (size_t)(rows + 1) * 8, hipMemcpyHostToDevice));
+  if (nnz) HIP_TRY(hipMemcpy(dVals.get(), vals, (size_t)nnz * ts, hipMemcpyHostToDevice));
   if (types && nnz) {
-    HIP_TRY(hipMalloc(&dTypes.p, (size_t)nnz));
-    HIP_TRY(hipMemcpy(dTypes.p, types, (size_t)nnz, hipMemcpyHostToDevice));
+    HIP_TRY(hipMalloc(dTypes.put(), (size_t)nnz));
+    HIP_TRY(hipMemcpy(dTypes.get(), types, (size_t)nnz, hipMemcpyHostToDevice));
   }
-  EvPair evp;
-  HIP_TRY(evp.create());
-  const hipEvent_t e0 = evp.a, e1 = evp.b;
+  Event ev0, ev1;
+  HIP_TRY(hipEventCreate(ev0.put()));
+  HIP_TRY(hipEventCreate(ev1.put()));
+  const hipEvent_t e0 = ev0.get(), e1 = ev1.get();
   HIP_TRY(hipEventRecord(e0, nullptr));
   constexpr int64_t kLongRow = 2048;  // longer rows: a workgroup per segment of kStatsSegment ratings, then the segments in order
   std::vector<int32_t> longRows, segRow;
@@ -993,43 +960,43 @@ int ycnr_rating_stats(int dtype, int64_t rows, const int64_t *rowPtr, const void
     }
   }
   firstSeg.push_back((int64_t)segRow.size());
-  DevBuf dLong, dSegRow, dSegBeg, dFirst, dPartCnt, dPartSum;
+  DevPtr<void> dLong, dSegRow, dSegBeg, dFirst, dPartCnt, dPartSum;
   if (!longRows.empty()) {
-    HIP_TRY(hipMalloc(&dLong.p, longRows.size() * 4));
-    HIP_TRY(hipMalloc(&dSegRow.p, segRow.size() * 4));
-    HIP_TRY(hipMalloc(&dSegBeg.p, segBeg.size() * 8));
-    HIP_TRY(hipMalloc(&dFirst.p, firstSeg.size() * 8));
-    HIP_TRY(hipMalloc(&dPartCnt.p, segRow.size() * 4));
-    HIP_TRY(hipMalloc(&dPartSum.p, segRow.size() * 8));
-    HIP_TRY(hipMemcpy(dLong.p, longRows.data(), longRows.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dSegRow.p, segRow.data(), segRow.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dSegBeg.p, segBeg.data(), segBeg.size() * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dFirst.p, firstSeg.data(), firstSeg.size() * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMalloc(dLong.put(), longRows.size() * 4));
+    HIP_TRY(hipMalloc(dSegRow.put(), segRow.size() * 4));
+    HIP_TRY(hipMalloc(dSegBeg.put(), segBeg.size() * 8));
+    HIP_TRY(hipMalloc(dFirst.put(), firstSeg.size() * 8));
+    HIP_TRY(hipMalloc(dPartCnt.put(), segRow.size() * 4));
+    HIP_TRY(hipMalloc(dPartSum.put(), segRow.size() * 8));
+    HIP_TRY(hipMemcpy(dLong.get(), longRows.data(), longRows.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dSegRow.get(), segRow.data(), segRow.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dSegBeg.get(), segBeg.data(), segBeg.size() * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dFirst.get(), firstSeg.data(), firstSeg.size() * 8, hipMemcpyHostToDevice));
   }
   HIP_TRY(hipEventRecord(e0, nullptr));
   const unsigned blocks = (unsigned)((rows * 16 + 255) / 256);
   const unsigned nSeg = (unsigned)segRow.size(), nLong = (unsigned)longRows.size();
   if (dtype == YCNR_F32) {
     if (nLong)  // (first: its workgroups are the long ones)
-      hipLaunchKernelGGL(rating_stats_long_kernel<float>, dim3(nSeg), dim3(256), 0, nullptr, (const int64_t *)dPtr.p, (const int32_t *)dSegRow.p,
-                         (const int64_t *)dSegBeg.p, (const float *)dVals.p, (const int8_t *)dTypes.p, (int32_t *)dPartCnt.p, (double *)dPartSum.p);
-    hipLaunchKernelGGL(rating_stats_kernel<float>, dim3(blocks), dim3(256), 0, nullptr, (const int64_t *)dPtr.p, rows,
-                       (const float *)dVals.p, (const int8_t *)dTypes.p, (int32_t *)dCnt.p, (double *)dSum.p, kLongRow);
+      hipLaunchKernelGGL(rating_stats_long_kernel<float>, dim3(nSeg), dim3(256), 0, nullptr, (const int64_t *)dPtr.get(), (const int32_t *)dSegRow.get(),
+                         (const int64_t *)dSegBeg.get(), (const float *)dVals.get(), (const int8_t *)dTypes.get(), (int32_t *)dPartCnt.get(), (double *)dPartSum.get());
+    hipLaunchKernelGGL(rating_stats_kernel<float>, dim3(blocks), dim3(256), 0, nullptr, (const int64_t *)dPtr.get(), rows,
+                       (const float *)dVals.get(), (const int8_t *)dTypes.get(), (int32_t *)dCnt.get(), (double *)dSum.get(), kLongRow);
   } else {
     if (nLong)
-      hipLaunchKernelGGL(rating_stats_long_kernel<double>, dim3(nSeg), dim3(256), 0, nullptr, (const int64_t *)dPtr.p, (const int32_t *)dSegRow.p,
-                         (const int64_t *)dSegBeg.p, (const double *)dVals.p, (const int8_t *)dTypes.p, (int32_t *)dPartCnt.p, (double *)dPartSum.p);
-    hipLaunchKernelGGL(rating_stats_kernel<double>, dim3(blocks), dim3(256), 0, nullptr, (const int64_t *)dPtr.p, rows,
-                       (const double *)dVals.p, (const int8_t *)dTypes.p, (int32_t *)dCnt.p, (double *)dSum.p, kLongRow);
+      hipLaunchKernelGGL(rating_stats_long_kernel<double>, dim3(nSeg), dim3(256), 0, nullptr, (const int64_t *)dPtr.get(), (const int32_t *)dSegRow.get(),
+                         (const int64_t *)dSegBeg.get(), (const double *)dVals.get(), (const int8_t *)dTypes.get(), (int32_t *)dPartCnt.get(), (double *)dPartSum.get());
+    hipLaunchKernelGGL(rating_stats_kernel<double>, dim3(blocks), dim3(256), 0, nullptr, (const int64_t *)dPtr.get(), rows,
+                       (const double *)dVals.get(), (const int8_t *)dTypes.get(), (int32_t *)dCnt.get(), (double *)dSum.get(), kLongRow);
   }
   if (nLong)
-    hipLaunchKernelGGL(rating_stats_combine_kernel, dim3((nLong + 255) / 256), dim3(256), 0, nullptr, (const int32_t *)dLong.p, (const int64_t *)dFirst.p,
-                       (int64_t)nLong, (const int32_t *)dPartCnt.p, (const double *)dPartSum.p, (int32_t *)dCnt.p, (double *)dSum.p);
+    hipLaunchKernelGGL(rating_stats_combine_kernel, dim3((nLong + 255) / 256), dim3(256), 0, nullptr, (const int32_t *)dLong.get(), (const int64_t *)dFirst.get(),
+                       (int64_t)nLong, (const int32_t *)dPartCnt.get(), (const double *)dPartSum.get(), (int32_t *)dCnt.get(), (double *)dSum.get());
   hipError_t le = hipGetLastError();
   int rc = le == hipSuccess ? timed(e0, e1, deviceMs) : fail(YCNR_ERR_HIP, "rating_stats launch: %s", hipGetErrorString(le));
   if (rc) return rc;
-  HIP_TRY(hipMemcpy(cnt, dCnt.p, (size_t)rows * 4, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(sum, dSum.p, (size_t)rows * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(cnt, dCnt.get(), (size_t)rows * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(sum, dSum.get(), (size_t)rows * 8, hipMemcpyDeviceToHost));
   return YCNR_OK;
 }
 
@@ -1047,39 +1014,40 @@ int bits_for(int64_t n) {
 int sort_and_unpack(int dtype, int64_t n, int64_t outRows, int64_t outCols, uint64_t *dKeys, uint32_t *dPos, const void *dVals,
                     int64_t *rowPtr, int32_t *indx, void *outVals, const std::function<void()> &makeKeys, double *deviceMs) {
   const size_t ts = tsize(dtype);
-  DevBuf dKeys2, dPos2, dTmp, dIndx, dOutVals, dPtr;
-  HIP_TRY(hipMalloc(&dKeys2.p, (size_t)n * 8));
-  HIP_TRY(hipMalloc(&dPos2.p, (size_t)n * 4));
-  HIP_TRY(hipMalloc(&dIndx.p, (size_t)n * 4));
-  HIP_TRY(hipMalloc(&dOutVals.p, (size_t)n * ts));
-  HIP_TRY(hipMalloc(&dPtr.p, (size_t)(outRows + 1) * 8));
+  DevPtr<void> dKeys2, dPos2, dTmp, dIndx, dOutVals, dPtr;
+  HIP_TRY(hipMalloc(dKeys2.put(), (size_t)n * 8));
+  HIP_TRY(hipMalloc(dPos2.put(), (size_t)n * 4));
+  HIP_TRY(hipMalloc(dIndx.put(), (size_t)n * 4));
+  HIP_TRY(hipMalloc(dOutVals.put(), (size_t)n * ts));
+  HIP_TRY(hipMalloc(dPtr.put(), (size_t)(outRows + 1) * 8));
   size_t tmpBytes = 0;
   const int colBits = bits_for(outCols), endBit = colBits + bits_for(outRows);
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmpBytes, dKeys, (uint64_t *)dKeys2.p, dPos, (uint32_t *)dPos2.p, (int)n, 0, endBit));
-  HIP_TRY(hipMalloc(&dTmp.p, std::max<size_t>(tmpBytes, 8)));
-  EvPair evp;
-  HIP_TRY(evp.create());
-  const hipEvent_t e0 = evp.a, e1 = evp.b;
+  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmpBytes, dKeys, (uint64_t *)dKeys2.get(), dPos, (uint32_t *)dPos2.get(), (int)n, 0, endBit));
+  HIP_TRY(hipMalloc(dTmp.put(), std::max<size_t>(tmpBytes, 8)));
+  Event ev0, ev1;
+  HIP_TRY(hipEventCreate(ev0.put()));
+  HIP_TRY(hipEventCreate(ev1.put()));
+  const hipEvent_t e0 = ev0.get(), e1 = ev1.get();
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipEventRecord(e0, nullptr));
   makeKeys();
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(dTmp.p, tmpBytes, dKeys, (uint64_t *)dKeys2.p, dPos, (uint32_t *)dPos2.p, (int)n, 0, endBit));
+  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(dTmp.get(), tmpBytes, dKeys, (uint64_t *)dKeys2.get(), dPos, (uint32_t *)dPos2.get(), (int)n, 0, endBit));
   const unsigned b256 = (unsigned)((n + 255) / 256);
   if (dtype == YCNR_F32)
-    hipLaunchKernelGGL(unpack_sorted_kernel<float>, dim3(b256), dim3(256), 0, nullptr, (const uint64_t *)dKeys2.p, (const uint32_t *)dPos2.p,
-                       (const float *)dVals, n, colBits, (int32_t *)dIndx.p, (float *)dOutVals.p);
+    hipLaunchKernelGGL(unpack_sorted_kernel<float>, dim3(b256), dim3(256), 0, nullptr, (const uint64_t *)dKeys2.get(), (const uint32_t *)dPos2.get(),
+                       (const float *)dVals, n, colBits, (int32_t *)dIndx.get(), (float *)dOutVals.get());
   else
-    hipLaunchKernelGGL(unpack_sorted_kernel<double>, dim3(b256), dim3(256), 0, nullptr, (const uint64_t *)dKeys2.p, (const uint32_t *)dPos2.p,
-                       (const double *)dVals, n, colBits, (int32_t *)dIndx.p, (double *)dOutVals.p);
-  hipLaunchKernelGGL(row_ptr_kernel, dim3((unsigned)((outRows + 1 + 255) / 256)), dim3(256), 0, nullptr, (const uint64_t *)dKeys2.p, n, outRows, colBits,
-                     (int64_t *)dPtr.p);
+    hipLaunchKernelGGL(unpack_sorted_kernel<double>, dim3(b256), dim3(256), 0, nullptr, (const uint64_t *)dKeys2.get(), (const uint32_t *)dPos2.get(),
+                       (const double *)dVals, n, colBits, (int32_t *)dIndx.get(), (double *)dOutVals.get());
+  hipLaunchKernelGGL(row_ptr_kernel, dim3((unsigned)((outRows + 1 + 255) / 256)), dim3(256), 0, nullptr, (const uint64_t *)dKeys2.get(), n, outRows, colBits,
+                     (int64_t *)dPtr.get());
   hipError_t le = hipGetLastError();
   if (le != hipSuccess) return fail(YCNR_ERR_HIP, "csr build: %s", hipGetErrorString(le));
   int rc = timed(e0, e1, deviceMs);
   if (rc) return rc;
-  HIP_TRY(hipMemcpy(rowPtr, dPtr.p, (size_t)(outRows + 1) * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(indx, dIndx.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(outVals, dOutVals.p, (size_t)n * ts, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(rowPtr, dPtr.get(), (size_t)(outRows + 1) * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(indx, dIndx.get(), (size_t)n * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(outVals, dOutVals.get(), (size_t)n * ts, hipMemcpyDeviceToHost));
   return YCNR_OK;
 }
 }  // namespace
@@ -1100,20 +1068,20 @@ int ycnr_csr_from_triplets(int dtype, int64_t n, const int32_t *rowIdx, const in
       return fail(YCNR_ERR_INVALID, "triplet %lld: (%d, %d) outside %lld x %lld", (long long)q, rowIdx[q], colIdx[q], (long long)rows,
                   (long long)cols);
   const size_t ts = tsize(dtype);
-  DevBuf dR, dC, dV, dKeys, dPos;
-  HIP_TRY(hipMalloc(&dR.p, (size_t)n * 4));
-  HIP_TRY(hipMalloc(&dC.p, (size_t)n * 4));
-  HIP_TRY(hipMalloc(&dV.p, (size_t)n * ts));
-  HIP_TRY(hipMalloc(&dKeys.p, (size_t)n * 8));
-  HIP_TRY(hipMalloc(&dPos.p, (size_t)n * 4));
-  HIP_TRY(hipMemcpy(dR.p, rowIdx, (size_t)n * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dC.p, colIdx, (size_t)n * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dV.p, vals, (size_t)n * ts, hipMemcpyHostToDevice));
+  DevPtr<void> dR, dC, dV, dKeys, dPos;
+  HIP_TRY(hipMalloc(dR.put(), (size_t)n * 4));
+  HIP_TRY(hipMalloc(dC.put(), (size_t)n * 4));
+  HIP_TRY(hipMalloc(dV.put(), (size_t)n * ts));
+  HIP_TRY(hipMalloc(dKeys.put(), (size_t)n * 8));
+  HIP_TRY(hipMalloc(dPos.put(), (size_t)n * 4));
+  HIP_TRY(hipMemcpy(dR.get(), rowIdx, (size_t)n * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dC.get(), colIdx, (size_t)n * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dV.get(), vals, (size_t)n * ts, hipMemcpyHostToDevice));
   auto makeKeys = [&] {
-    hipLaunchKernelGGL(make_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, (const int32_t *)dR.p, (const int32_t *)dC.p, n,
-                       bits_for(cols), (uint64_t *)dKeys.p, (uint32_t *)dPos.p);
+    hipLaunchKernelGGL(make_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, (const int32_t *)dR.get(), (const int32_t *)dC.get(), n,
+                       bits_for(cols), (uint64_t *)dKeys.get(), (uint32_t *)dPos.get());
   };
-  return sort_and_unpack(dtype, n, rows, cols, (uint64_t *)dKeys.p, (uint32_t *)dPos.p, dV.p, rowPtr, indx, outVals, makeKeys, deviceMs);
+  return sort_and_unpack(dtype, n, rows, cols, (uint64_t *)dKeys.get(), (uint32_t *)dPos.get(), dV.get(), rowPtr, indx, outVals, makeKeys, deviceMs);
 }
 
 int ycnr_csr_transpose(int dtype, int64_t rows, int64_t cols, const int64_t *rowPtr, const int32_t *indx, const void *vals,
@@ -1134,49 +1102,50 @@ int ycnr_csr_transpose(int dtype, int64_t rows, int64_t cols, const int64_t *row
   for (int64_t q = 0; q < n; ++q)
     if (indx[q] < 0 || indx[q] >= cols) return fail(YCNR_ERR_INVALID, "entry %lld: column %d outside %lld", (long long)q, indx[q], (long long)cols);
   const size_t ts = tsize(dtype);
-  DevBuf dP, dI, dV, dPos, dRowOf, dKeys2, dPos2, dTmp, dIndx, dOutVals, dPtr;
-  HIP_TRY(hipMalloc(&dP.p, (size_t)(rows + 1) * 8));
-  HIP_TRY(hipMalloc(&dI.p, (size_t)n * 4));
-  HIP_TRY(hipMalloc(&dV.p, (size_t)n * ts));
-  HIP_TRY(hipMalloc(&dPos.p, (size_t)n * 4));
-  HIP_TRY(hipMalloc(&dRowOf.p, (size_t)n * 4));
-  HIP_TRY(hipMalloc(&dKeys2.p, (size_t)n * 4));
-  HIP_TRY(hipMalloc(&dPos2.p, (size_t)n * 4));
-  HIP_TRY(hipMalloc(&dIndx.p, (size_t)n * 4));
-  HIP_TRY(hipMalloc(&dOutVals.p, (size_t)n * ts));
-  HIP_TRY(hipMalloc(&dPtr.p, (size_t)(cols + 1) * 8));
-  HIP_TRY(hipMemcpy(dP.p, rowPtr, (size_t)(rows + 1) * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dI.p, indx, (size_t)n * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dV.p, vals, (size_t)n * ts, hipMemcpyHostToDevice));
+  DevPtr<void> dP, dI, dV, dPos, dRowOf, dKeys2, dPos2, dTmp, dIndx, dOutVals, dPtr;
+  HIP_TRY(hipMalloc(dP.put(), (size_t)(rows + 1) * 8));
+  HIP_TRY(hipMalloc(dI.put(), (size_t)n * 4));
+  HIP_TRY(hipMalloc(dV.put(), (size_t)n * ts));
+  HIP_TRY(hipMalloc(dPos.put(), (size_t)n * 4));
+  HIP_TRY(hipMalloc(dRowOf.put(), (size_t)n * 4));
+  HIP_TRY(hipMalloc(dKeys2.put(), (size_t)n * 4));
+  HIP_TRY(hipMalloc(dPos2.put(), (size_t)n * 4));
+  HIP_TRY(hipMalloc(dIndx.put(), (size_t)n * 4));
+  HIP_TRY(hipMalloc(dOutVals.put(), (size_t)n * ts));
+  HIP_TRY(hipMalloc(dPtr.put(), (size_t)(cols + 1) * 8));
+  HIP_TRY(hipMemcpy(dP.get(), rowPtr, (size_t)(rows + 1) * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dI.get(), indx, (size_t)n * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dV.get(), vals, (size_t)n * ts, hipMemcpyHostToDevice));
   // a stable sort of the positions by column id alone (prep_kernels.hip.h): the ids are non-negative, so they sort as uint32
   size_t tmpBytes = 0;
   const int endBit = bits_for(cols);
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmpBytes, (const uint32_t *)dI.p, (uint32_t *)dKeys2.p, (const uint32_t *)dPos.p,
-                                             (uint32_t *)dPos2.p, (int)n, 0, endBit));
-  HIP_TRY(hipMalloc(&dTmp.p, std::max<size_t>(tmpBytes, 8)));
-  EvPair evp;
-  HIP_TRY(evp.create());
-  const hipEvent_t e0 = evp.a, e1 = evp.b;
+  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmpBytes, (const uint32_t *)dI.get(), (uint32_t *)dKeys2.get(), (const uint32_t *)dPos.get(),
+                                             (uint32_t *)dPos2.get(), (int)n, 0, endBit));
+  HIP_TRY(hipMalloc(dTmp.put(), std::max<size_t>(tmpBytes, 8)));
+  Event ev0, ev1;
+  HIP_TRY(hipEventCreate(ev0.put()));
+  HIP_TRY(hipEventCreate(ev1.put()));
+  const hipEvent_t e0 = ev0.get(), e1 = ev1.get();
   HIP_TRY(hipEventRecord(e0, nullptr));
   const unsigned b256 = (unsigned)((n + 255) / 256);
-  hipLaunchKernelGGL(iota_rows_kernel, dim3(b256), dim3(256), 0, nullptr, (const int64_t *)dP.p, rows, n, (uint32_t *)dPos.p, (int32_t *)dRowOf.p);
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(dTmp.p, tmpBytes, (const uint32_t *)dI.p, (uint32_t *)dKeys2.p, (const uint32_t *)dPos.p,
-                                             (uint32_t *)dPos2.p, (int)n, 0, endBit));
+  hipLaunchKernelGGL(iota_rows_kernel, dim3(b256), dim3(256), 0, nullptr, (const int64_t *)dP.get(), rows, n, (uint32_t *)dPos.get(), (int32_t *)dRowOf.get());
+  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(dTmp.get(), tmpBytes, (const uint32_t *)dI.get(), (uint32_t *)dKeys2.get(), (const uint32_t *)dPos.get(),
+                                             (uint32_t *)dPos2.get(), (int)n, 0, endBit));
   if (dtype == YCNR_F32)
-    hipLaunchKernelGGL(unpack_transposed_kernel<float>, dim3(b256), dim3(256), 0, nullptr, (const uint32_t *)dPos2.p, (const int32_t *)dRowOf.p,
-                       (const float *)dV.p, n, (int32_t *)dIndx.p, (float *)dOutVals.p);
+    hipLaunchKernelGGL(unpack_transposed_kernel<float>, dim3(b256), dim3(256), 0, nullptr, (const uint32_t *)dPos2.get(), (const int32_t *)dRowOf.get(),
+                       (const float *)dV.get(), n, (int32_t *)dIndx.get(), (float *)dOutVals.get());
   else
-    hipLaunchKernelGGL(unpack_transposed_kernel<double>, dim3(b256), dim3(256), 0, nullptr, (const uint32_t *)dPos2.p, (const int32_t *)dRowOf.p,
-                       (const double *)dV.p, n, (int32_t *)dIndx.p, (double *)dOutVals.p);
-  hipLaunchKernelGGL(row_ptr32_kernel, dim3((unsigned)((cols + 1 + 255) / 256)), dim3(256), 0, nullptr, (const uint32_t *)dKeys2.p, n, cols,
-                     (int64_t *)dPtr.p);
+    hipLaunchKernelGGL(unpack_transposed_kernel<double>, dim3(b256), dim3(256), 0, nullptr, (const uint32_t *)dPos2.get(), (const int32_t *)dRowOf.get(),
+                       (const double *)dV.get(), n, (int32_t *)dIndx.get(), (double *)dOutVals.get());
+  hipLaunchKernelGGL(row_ptr32_kernel, dim3((unsigned)((cols + 1 + 255) / 256)), dim3(256), 0, nullptr, (const uint32_t *)dKeys2.get(), n, cols,
+                     (int64_t *)dPtr.get());
   hipError_t le = hipGetLastError();
   if (le != hipSuccess) return fail(YCNR_ERR_HIP, "csr transpose: %s", hipGetErrorString(le));
   int rc = timed(e0, e1, deviceMs);
   if (rc) return rc;
-  HIP_TRY(hipMemcpy(outPtr, dPtr.p, (size_t)(cols + 1) * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(outIndx, dIndx.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(outVals, dOutVals.p, (size_t)n * ts, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(outPtr, dPtr.get(), (size_t)(cols + 1) * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(outIndx, dIndx.get(), (size_t)n * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(outVals, dOutVals.get(), (size_t)n * ts, hipMemcpyDeviceToHost));
   return YCNR_OK;
 }
 
@@ -1205,28 +1174,29 @@ int ycnr_recommend_items(int dtype, int32_t k, int64_t nUsers, const void *userR
   const int take = limit - 1;  // lib/YcnrController.js:268-269
   // users in batches whose score matrix stays below 1 GB
   const int64_t batch = std::max<int64_t>(1, std::min<int64_t>(nUsers, ((int64_t)1 << 27) / std::max<int64_t>(1, totalItems)));
-  DevBuf dItems, dUsers, dSkipPtr, dSkip, dScores, dIds, dPred, dCnt;
-  HIP_TRY(hipMalloc(&dItems.p, std::max<size_t>((size_t)totalItems * k * ts, 8)));
-  HIP_TRY(hipMalloc(&dUsers.p, (size_t)batch * k * ts));
-  HIP_TRY(hipMalloc(&dSkipPtr.p, (size_t)(batch + 1) * 8));
-  HIP_TRY(hipMalloc(&dSkip.p, std::max<size_t>((size_t)nSkip * 4, 8)));
-  HIP_TRY(hipMalloc(&dScores.p, std::max<size_t>((size_t)batch * totalItems * 8, 8)));
-  HIP_TRY(hipMalloc(&dIds.p, (size_t)batch * limit * 4));
-  HIP_TRY(hipMalloc(&dPred.p, (size_t)batch * limit * 8));
-  HIP_TRY(hipMalloc(&dCnt.p, (size_t)batch * 4));
-  if (totalItems) HIP_TRY(hipMemcpy(dItems.p, itemFactors, (size_t)totalItems * k * ts, hipMemcpyHostToDevice));
-  if (nSkip) HIP_TRY(hipMemcpy(dSkip.p, skipIds, (size_t)nSkip * 4, hipMemcpyHostToDevice));
-  EvPair evp;
-  HIP_TRY(evp.create());
-  const hipEvent_t e0 = evp.a, e1 = evp.b;
+  DevPtr<void> dItems, dUsers, dSkipPtr, dSkip, dScores, dIds, dPred, dCnt;
+  HIP_TRY(hipMalloc(dItems.put(), std::max<size_t>((size_t)totalItems * k * ts, 8)));
+  HIP_TRY(hipMalloc(dUsers.put(), (size_t)batch * k * ts));
+  HIP_TRY(hipMalloc(dSkipPtr.put(), (size_t)(batch + 1) * 8));
+  HIP_TRY(hipMalloc(dSkip.put(), std::max<size_t>((size_t)nSkip * 4, 8)));
+  HIP_TRY(hipMalloc(dScores.put(), std::max<size_t>((size_t)batch * totalItems * 8, 8)));
+  HIP_TRY(hipMalloc(dIds.put(), (size_t)batch * limit * 4));
+  HIP_TRY(hipMalloc(dPred.put(), (size_t)batch * limit * 8));
+  HIP_TRY(hipMalloc(dCnt.put(), (size_t)batch * 4));
+  if (totalItems) HIP_TRY(hipMemcpy(dItems.get(), itemFactors, (size_t)totalItems * k * ts, hipMemcpyHostToDevice));
+  if (nSkip) HIP_TRY(hipMemcpy(dSkip.get(), skipIds, (size_t)nSkip * 4, hipMemcpyHostToDevice));
+  Event ev0, ev1;
+  HIP_TRY(hipEventCreate(ev0.put()));
+  HIP_TRY(hipEventCreate(ev1.put()));
+  const hipEvent_t e0 = ev0.get(), e1 = ev1.get();
   double total = 0.0;
   int rc = YCNR_OK;
   std::vector<int64_t> localPtr;
   for (int64_t u0 = 0; u0 < nUsers && !rc; u0 += batch) {
     const int64_t nb = std::min(batch, nUsers - u0);
     localPtr.assign(skipPtr + u0, skipPtr + u0 + nb + 1);  // absolute offsets into dSkip
-    HIP_TRY(hipMemcpy(dUsers.p, (const char *)userRows + (size_t)u0 * k * ts, (size_t)nb * k * ts, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dSkipPtr.p, localPtr.data(), (size_t)(nb + 1) * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dUsers.get(), (const char *)userRows + (size_t)u0 * k * ts, (size_t)nb * k * ts, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dSkipPtr.get(), localPtr.data(), (size_t)(nb + 1) * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipEventRecord(e0, nullptr));
     // scores on the matrix cores: 16 users per workgroup, the item tiles dealt over the waves of gridDim.y workgroups
     // (YCNR_RECOMMEND_VALU=1: the 16-lane-group kernel, one user per workgroup, for A/B runs)
@@ -1236,32 +1206,32 @@ int ycnr_recommend_items(int dtype, int32_t k, int64_t nUsers, const void *userR
     const bool valu = getenv("YCNR_RECOMMEND_VALU") != nullptr || 16 * kp * ts > 48 * 1024;  // (16 users' factors must fit the default LDS limit)
     if (dtype == YCNR_F32) {
       if (valu)
-        hipLaunchKernelGGL((recommend_scores_kernel<float, 1>), dim3((unsigned)nb), dim3(256), (size_t)k * ts, nullptr, (const float *)dUsers.p, nb,
-                           (const float *)dItems.p, totalItems, (int)k, globalAvgShift, minRecommendRating, (double *)dScores.p);
+        hipLaunchKernelGGL((recommend_scores_kernel<float, 1>), dim3((unsigned)nb), dim3(256), (size_t)k * ts, nullptr, (const float *)dUsers.get(), nb,
+                           (const float *)dItems.get(), totalItems, (int)k, globalAvgShift, minRecommendRating, (double *)dScores.get());
       else
-        hipLaunchKernelGGL(recommend_scores_mfma_kernel<float>, dim3(ublk, yblk), dim3(256), 16 * kp * ts, nullptr, (const float *)dUsers.p, nb,
-                           (const float *)dItems.p, totalItems, (int)k, globalAvgShift, minRecommendRating, (double *)dScores.p);
+        hipLaunchKernelGGL(recommend_scores_mfma_kernel<float>, dim3(ublk, yblk), dim3(256), 16 * kp * ts, nullptr, (const float *)dUsers.get(), nb,
+                           (const float *)dItems.get(), totalItems, (int)k, globalAvgShift, minRecommendRating, (double *)dScores.get());
     } else {
       if (valu)
-        hipLaunchKernelGGL((recommend_scores_kernel<double, 1>), dim3((unsigned)nb), dim3(256), (size_t)k * ts, nullptr, (const double *)dUsers.p, nb,
-                           (const double *)dItems.p, totalItems, (int)k, globalAvgShift, minRecommendRating, (double *)dScores.p);
+        hipLaunchKernelGGL((recommend_scores_kernel<double, 1>), dim3((unsigned)nb), dim3(256), (size_t)k * ts, nullptr, (const double *)dUsers.get(), nb,
+                           (const double *)dItems.get(), totalItems, (int)k, globalAvgShift, minRecommendRating, (double *)dScores.get());
       else
-        hipLaunchKernelGGL(recommend_scores_mfma_kernel<double>, dim3(ublk, yblk), dim3(256), 16 * kp * ts, nullptr, (const double *)dUsers.p, nb,
-                           (const double *)dItems.p, totalItems, (int)k, globalAvgShift, minRecommendRating, (double *)dScores.p);
+        hipLaunchKernelGGL(recommend_scores_mfma_kernel<double>, dim3(ublk, yblk), dim3(256), 16 * kp * ts, nullptr, (const double *)dUsers.get(), nb,
+                           (const double *)dItems.get(), totalItems, (int)k, globalAvgShift, minRecommendRating, (double *)dScores.get());
     }
     if (nSkip)
-      hipLaunchKernelGGL(recommend_skip_kernel, dim3((unsigned)nb), dim3(256), 0, nullptr, (const int64_t *)dSkipPtr.p, (const int32_t *)dSkip.p, totalItems,
-                         (double *)dScores.p);
-    hipLaunchKernelGGL(recommend_select_kernel, dim3((unsigned)nb), dim3(256), 0, nullptr, (double *)dScores.p, totalItems, take, (int)limit,
-                       (int32_t *)dIds.p, (double *)dPred.p, (int32_t *)dCnt.p);
+      hipLaunchKernelGGL(recommend_skip_kernel, dim3((unsigned)nb), dim3(256), 0, nullptr, (const int64_t *)dSkipPtr.get(), (const int32_t *)dSkip.get(), totalItems,
+                         (double *)dScores.get());
+    hipLaunchKernelGGL(recommend_select_kernel, dim3((unsigned)nb), dim3(256), 0, nullptr, (double *)dScores.get(), totalItems, take, (int)limit,
+                       (int32_t *)dIds.get(), (double *)dPred.get(), (int32_t *)dCnt.get());
     hipError_t le = hipGetLastError();
     double ms = 0.0;
     rc = le == hipSuccess ? timed(e0, e1, &ms) : fail(YCNR_ERR_HIP, "recommend launch: %s", hipGetErrorString(le));
     total += ms;
     if (rc) break;
-    HIP_TRY(hipMemcpy(outIds + u0 * limit, dIds.p, (size_t)nb * limit * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(outPredict + u0 * limit, dPred.p, (size_t)nb * limit * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(outCount + u0, dCnt.p, (size_t)nb * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(outIds + u0 * limit, dIds.get(), (size_t)nb * limit * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(outPredict + u0 * limit, dPred.get(), (size_t)nb * limit * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(outCount + u0, dCnt.get(), (size_t)nb * 4, hipMemcpyDeviceToHost));
   }
   if (deviceMs) *deviceMs = total;
   return rc;
@@ -1293,19 +1263,17 @@ int ycnr_als_create(const ycnr_als_options *o, ycnr_als **out) {
   h->autoChunk = h->opt.chunkRatings == 0;
   if (h->opt.chunkRatings == 0) h->opt.chunkRatings = kDefaultChunk;
   h->opt.chunkRatings = (h->opt.chunkRatings + 3) & ~3;
-  hipError_t e = hipStreamCreateWithFlags(&h->ownStream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreate(&h->evComputeEnd);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&h->evStepStart, hipEventDisableTiming);
+  hipError_t e = hipStreamCreateWithFlags(h->ownStream.put(), hipStreamNonBlocking);
+  if (e == hipSuccess) e = new_event(h->evComputeEnd, true);
+  if (e == hipSuccess) e = new_event(h->evStepStart, false);
   // (the side streams of the one-piece half-step are created when a half-step first needs them: every stream a process creates
   // takes a share of the runtime's 4 or 8 hardware queues, and a sharded run -- step's stream, two piece streams, the
   // communicator's stream -- must not find one of its streams behind another's event waits on a shared queue)
-  for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipStreamCreateWithFlags(&h->pieceStream[i], hipStreamNonBlocking);
+  for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipStreamCreateWithFlags(h->pieceStream[i].put(), hipStreamNonBlocking);
   for (int s = 0; s < 2 && e == hipSuccess; ++s) {
-    e = hipMalloc(&h->factors[s], (size_t)h->rows(s) * o->factorsCount * h->ts());
-    if (e == hipSuccess) {
-      h->ownFactors[s] = true;
-      e = hipMemsetAsync(h->factors[s], 0, (size_t)h->rows(s) * o->factorsCount * h->ts(), h->ownStream);
-    }
+    e = hipMalloc(h->factorsMem[s].put(), (size_t)h->rows(s) * o->factorsCount * h->ts());
+    h->factors[s] = h->factorsMem[s].get();
+    if (e == hipSuccess) e = hipMemsetAsync(h->factors[s], 0, (size_t)h->rows(s) * o->factorsCount * h->ts(), h->ownStream.get());
   }
   // float32 with factorsCount % 4 != 0: the kernels run on copies of the matrices padded to a multiple of 4 columns (zero columns:
   // lambda n on their diagonal, x = 0 there, the other columns' arithmetic unchanged) -- rows are then 16-byte aligned and every
@@ -1313,24 +1281,24 @@ int ycnr_als_create(const ycnr_als_options *o, ycnr_als **out) {
   // (round 3: k > 128 only; round 4: every k).  Costs a pad of the fixed side and an unpad of the solved rows per half-step.
   if (o->dtype == YCNR_F32 && o->factorsCount % 4 != 0 && (o->factorsCount > kMaxFactors || !getenv("YCNR_NO_KPAD_SMALL"))) {  // (the variable: A/B runs)
     h->kPad = (o->factorsCount + 3) & ~3;
-    for (int s = 0; s < 2 && e == hipSuccess; ++s) e = hipMalloc(&h->padded[s], (size_t)h->rows(s) * h->kPad * sizeof(float));
+    for (int s = 0; s < 2 && e == hipSuccess; ++s) e = hipMalloc(h->padded[s].put(), (size_t)h->rows(s) * h->kPad * sizeof(float));
   }
   h->copt = h->opt;
   if (h->kPad) h->copt.factorsCount = h->kPad;
-  if (e == hipSuccess) e = hipMalloc(&h->dErr, kErrBytes);  // ErrInfo + room for in-kernel stamps of diagnostic builds
-  if (e == hipSuccess) e = hipMemsetAsync(h->dErr, 0, kErrBytes, h->ownStream);
-  if (e == hipSuccess) e = hipHostMalloc((void **)&h->hErr, sizeof(ErrInfo), hipHostMallocDefault);
-  if (e == hipSuccess) memset(h->hErr, 0, sizeof(ErrInfo));
-  if (e == hipSuccess) e = hipMalloc(&h->dZeros, kZeroRowBytes);
-  if (e == hipSuccess) e = hipMemsetAsync(h->dZeros, 0, kZeroRowBytes, h->ownStream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->ownStream);
+  if (e == hipSuccess) e = hipMalloc((void **)h->dErr.put(), kErrBytes);  // ErrInfo + room for in-kernel stamps of diagnostic builds
+  if (e == hipSuccess) e = hipMemsetAsync(h->dErr.get(), 0, kErrBytes, h->ownStream.get());
+  if (e == hipSuccess) e = hipHostMalloc((void **)h->hErr.put(), sizeof(ErrInfo), hipHostMallocDefault);
+  if (e == hipSuccess) memset(h->hErr.get(), 0, sizeof(ErrInfo));
+  if (e == hipSuccess) e = hipMalloc(h->dZeros.put(), kZeroRowBytes);
+  if (e == hipSuccess) e = hipMemsetAsync(h->dZeros.get(), 0, kZeroRowBytes, h->ownStream.get());
+  if (e == hipSuccess) e = hipStreamSynchronize(h->ownStream.get());
   if (e != hipSuccess) {
     int code = fail(e == hipErrorOutOfMemory ? YCNR_ERR_NOMEM : YCNR_ERR_HIP, "ycnr_als_create: %s",
                     hipGetErrorString(e));
     ycnr_als_destroy(h);
     return code;
   }
-  h->stream = h->ownStream;
+  h->stream = h->ownStream.get();
   *out = h;
   return YCNR_OK;
 }
@@ -1341,38 +1309,7 @@ int ycnr_als_destroy(ycnr_als *h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   h->drop_graphs();
   comm_release(h->comm);
-  for (int s = 0; s < 2; ++s) {
-    for (Part &p : h->parts[s]) p.release();
-    h->parts[s].clear();
-    h->banded[s].release();
-    h->rmse[s].release();
-    if (h->ownFactors[s] && h->factors[s]) (void)hipFree(h->factors[s]);
-    if (h->padded[s]) (void)hipFree(h->padded[s]);
-    if (h->planes[s]) (void)hipFree(h->planes[s]);
-  }
-  for (ycnr_als::RecBuf &b : h->rec)
-    if (b.p) (void)hipFree(b.p);
-  for (hipEvent_t ev : h->recEv)
-    if (ev) (void)hipEventDestroy(ev);
-  if (h->dErr) (void)hipFree(h->dErr);
-  if (h->hErr) (void)hipHostFree(h->hErr);
-  if (h->dZeros) (void)hipFree(h->dZeros);
-  if (h->evComputeEnd) (void)hipEventDestroy(h->evComputeEnd);
-  if (h->evStepStart) (void)hipEventDestroy(h->evStepStart);
-  for (int i = 0; i < kSideStreams; ++i) {
-    if (h->sideStream[i]) {
-      (void)hipStreamSynchronize(h->sideStream[i]);
-      (void)hipStreamDestroy(h->sideStream[i]);
-    }
-  }
-  for (int i = 0; i < 2; ++i) {
-    if (h->pieceStream[i]) {
-      (void)hipStreamSynchronize(h->pieceStream[i]);
-      (void)hipStreamDestroy(h->pieceStream[i]);
-    }
-  }
-  if (h->ownStream) (void)hipStreamDestroy(h->ownStream);
-  delete h;
+  delete h;  // the members free what they own; the streams go last (their place in the struct)
   return YCNR_OK;
 }
 
@@ -1381,7 +1318,7 @@ int ycnr_als_set_stream(ycnr_als *h, void *s) {
   HIP_TRY(hipSetDevice(h->opt.device));
   HIP_TRY(hipStreamSynchronize(h->stream));
   h->drop_graphs();
-  h->stream = s == YCNR_OWN_STREAM ? h->ownStream : (hipStream_t)s;  // NULL = the null (default) stream
+  h->stream = s == YCNR_OWN_STREAM ? h->ownStream.get() : (hipStream_t)s;  // NULL = the null (default) stream
   return YCNR_OK;
 }
 
@@ -1407,32 +1344,33 @@ static int upload_ratings(ycnr_als *h, Ratings &R, int64_t totalRows, int64_t op
                                                  (long long)(rowBegin + r));
   if (hostPtr[0] < 0) return fail(YCNR_ERR_INVALID, "%s: negative rowPtr", what);
   const int64_t base = hostPtr[0], nnz = hostPtr[nRows] - base;
-  R.release();
-  R.rowBegin = rowBegin;
-  R.rowEnd = rowEnd;
-  R.nnz = nnz;
+  R = Ratings();  // what the destination held goes before the new arrays are allocated; a failure below leaves it unloaded
+  Ratings N;      // (an early return frees what has been built)
+  N.rowBegin = rowBegin;
+  N.rowEnd = rowEnd;
+  N.nnz = nnz;
   const size_t ts = h->ts();
   // 64 bytes of slack: the bf16x6 kernel reads ids and ratings with 16-byte vector loads
-  HIP_TRY(hipMalloc(&R.dIndx, (size_t)nnz * 4 + 64));
-  HIP_TRY(hipMalloc(&R.dVals, (size_t)nnz * ts + 64));
-  int rc = copy_in(R.dIndx, indx + base, (size_t)nnz * 4, memKind, h->stream);
+  HIP_TRY(hipMalloc(N.dIndx.put(), (size_t)nnz * 4 + 64));
+  HIP_TRY(hipMalloc(N.dVals.put(), (size_t)nnz * ts + 64));
+  int rc = copy_in(N.dIndx.get(), indx + base, (size_t)nnz * 4, memKind, h->stream);
   if (rc) return rc;
-  rc = copy_in(R.dVals, (const char *)vals + (size_t)base * ts, (size_t)nnz * ts, memKind, h->stream);
+  rc = copy_in(N.dVals.get(), (const char *)vals + (size_t)base * ts, (size_t)nnz * ts, memKind, h->stream);
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(h->stream));
-  rc = check_index_range(R.dIndx, nnz, oppositeRows, h->stream, what);
-  if (rc) {
-    R.release();
-    return rc;
-  }
-  R.loaded = true;
+  rc = check_index_range(N.dIndx.get(), nnz, oppositeRows, h->stream, what);
+  if (rc) return rc;
+  N.loaded = true;
+  R = std::move(N);
   return YCNR_OK;
 }
 
-// Upload + schedule (schedule.h) of one piece [rowBegin, rowEnd) of a side's rows into newR / S (both released
-// by the caller when this fails).
+// Upload + schedule (schedule.h) of one piece [rowBegin, rowEnd) of a side's rows into part.R / part.S, which
+// are written only when everything is built (an early return frees what it has made so far).
 static int build_part(ycnr_als *h, int side, const int64_t *rowPtr, const int32_t *indx, const void *vals, int64_t rowBegin,
-                      int64_t rowEnd, int memKind, Ratings &newR, Schedule &S, SideNnz sideNnz) {
+                      int64_t rowEnd, int memKind, Part &part, SideNnz sideNnz) {
+  Ratings newR;
+  Schedule S;
   std::vector<int64_t> hp;
   int rc = upload_ratings(h, newR, h->rows(side), h->rows(1 - side), rowPtr, indx, vals, rowBegin,
                           rowEnd, memKind, hp, side == YCNR_BY_USER ? "set_ratings(byUser)" : "set_ratings(byItem)");
@@ -1459,7 +1397,7 @@ static int build_part(ycnr_als *h, int side, const int64_t *rowPtr, const int32_
       const int nBands = (int)((fixedRows + W - 1) / W);
       const BoundQueries q = band_queries(plan, hp.data(), rowBegin, W, nBands);
       std::vector<int64_t> cuts;
-      if (int rc2 = lower_bound_i32(newR.dIndx, q.beg, q.end, q.key, cuts, h->stream)) return rc2;
+      if (int rc2 = lower_bound_i32(newR.dIndx.get(), q.beg, q.end, q.key, cuts, h->stream)) return rc2;
       const BandCutError bad = band_recut(plan, hp.data(), rowBegin, P, nBands, cuts);
       if (bad.parts) return fail(YCNR_ERR_STATE, "band schedule: %d chunks for row %d", bad.parts, bad.row);
     }
@@ -1472,17 +1410,19 @@ static int build_part(ycnr_als *h, int side, const int64_t *rowPtr, const int32_
     int64_t batchRows = kPairBatchRows;
     if (const char *e = getenv("YCNR_PAIR_BATCH_ROWS")) batchRows = std::max(256, atoi(e));  // read per upload
     S.rowSlabRows = std::min<int64_t>(S.nPrimal, batchRows);
-    HIP_TRY(hipMalloc(&S.dRowSlabs, (size_t)S.rowSlabRows * (size_t)wg_slab_floats(kPairNB) * sizeof(float)));
+    HIP_TRY(hipMalloc(S.dRowSlabs.put(), (size_t)S.rowSlabRows * (size_t)wg_slab_floats(kPairNB) * sizeof(float)));
   }
   if (S.nUnits) {
-    HIP_TRY(hipMalloc(&S.dUnits, sizeof(Unit) * plan.units.size()));
-    HIP_TRY(hipMemcpy(S.dUnits, plan.units.data(), sizeof(Unit) * plan.units.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMalloc(S.dUnits.put(), sizeof(Unit) * plan.units.size()));
+    HIP_TRY(hipMemcpy(S.dUnits.get(), plan.units.data(), sizeof(Unit) * plan.units.size(), hipMemcpyHostToDevice));
   }
   if (S.nSplit) {
-    HIP_TRY(hipMalloc(&S.dSplit, sizeof(SplitRow) * plan.split.size()));
-    HIP_TRY(hipMemcpy(S.dSplit, plan.split.data(), sizeof(SplitRow) * plan.split.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc(&S.dSlabs, (size_t)S.arenaSlabs * slabElems * h->ts()));
+    HIP_TRY(hipMalloc(S.dSplit.put(), sizeof(SplitRow) * plan.split.size()));
+    HIP_TRY(hipMemcpy(S.dSplit.get(), plan.split.data(), sizeof(SplitRow) * plan.split.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMalloc(S.dSlabs.put(), (size_t)S.arenaSlabs * slabElems * h->ts()));
   }
+  part.R = std::move(newR);
+  part.S = std::move(S);
   return YCNR_OK;
 }
 
@@ -1492,15 +1432,7 @@ static int build_part(ycnr_als *h, int side, const int64_t *rowPtr, const int32_
 // never new ratings with an old schedule.
 static int set_ratings_parts(ycnr_als *h, int side, const int64_t *rowPtr, const int32_t *indx, const void *vals, int memKind,
                              int nParts, const int64_t *b) {
-  struct Pending {
-    std::vector<Part> parts;
-    bool keep = false;
-    ~Pending() {
-      if (!keep)
-        for (Part &p : parts) p.release();
-    }
-  } pend;
-  pend.parts.resize((size_t)nParts);
+  std::vector<Part> parts((size_t)nParts);
   // The ratings of the WHOLE side that sit in rows long enough to be split (rowPtr describes every row of the side, whatever
   // shard this handle solves): what the automatic chunk length is sized for.  MAL scale: nearly all of the item side's 121 M
   // ratings (-> 3072), a few per cent of the user side's (-> 1024: its chunk kernel is a few hundred waves whose length is
@@ -1519,20 +1451,17 @@ static int set_ratings_parts(ycnr_als *h, int side, const int64_t *rowPtr, const
     sideNnz = side_nnz(rp, nr);
   }
   for (int i = 0; i < nParts; ++i) {
-    Part &p = pend.parts[(size_t)i];
+    Part &p = parts[(size_t)i];
     hipError_t e = p.create_events();
     if (e != hipSuccess) return fail(YCNR_ERR_HIP, "set_ratings: hipEventCreate: %s", hipGetErrorString(e));
-    int rc = build_part(h, side, rowPtr, indx, vals, b[i], b[i + 1], memKind, p.R, p.S, sideNnz);
+    int rc = build_part(h, side, rowPtr, indx, vals, b[i], b[i + 1], memKind, p, sideNnz);
     if (rc) return rc;
   }
   HIP_TRY(hipStreamSynchronize(h->stream));  // nothing in flight still reads the previous upload
-  for (Part &p : h->parts[side]) p.release();
-  h->banded[side].release();
+  h->banded[side] = BandedSide();
   h->deferExchange[side] = false;  // (a new upload exchanges after every half-step again until the host says otherwise)
   h->drop_graphs();
-  h->parts[side].swap(pend.parts);
-  pend.parts.clear();
-  pend.keep = true;
+  h->parts[side].swap(parts);  // the previous upload is freed as `parts` goes out of scope
   return YCNR_OK;
 }
 
@@ -1610,19 +1539,9 @@ int ycnr_als_set_ratings_banded(ycnr_als *h, int side, const int64_t *rowPtr, co
   for (int r = 0; r < world; ++r)
     if (rankBands[r + 1] < rankBands[r] || ownerBounds[r + 1] < ownerBounds[r]) return fail(YCNR_ERR_INVALID, "set_ratings_banded: rankBands / ownerBounds must ascend");
   HIP_TRY(hipSetDevice(h->opt.device));
-  struct Pending {
-    Part part;
-    BandedSide B;
-    bool keep = false;
-    ~Pending() {
-      if (!keep) {
-        part.release();
-        B.release();
-      }
-    }
-  } pend;
-  Part &part = pend.part;
-  BandedSide &B = pend.B;
+  std::vector<Part> staged(1);  // staged in locals: a failure frees them and leaves the previous upload intact
+  Part &part = staged[0];
+  BandedSide B;
   int rc = YCNR_OK;
   const size_t ts = h->ts();
   const int bl = (int)rankBands[rank], bh = (int)rankBands[rank + 1], bpr = bh - bl;
@@ -1630,14 +1549,14 @@ int ycnr_als_set_ratings_banded(ycnr_als *h, int side, const int64_t *rowPtr, co
   std::vector<double> counts((size_t)rows * (size_t)nBands, 0.0);
   auto build = [&]() -> int {
     hipError_t e = part.create_events();
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&B.evRecv, hipEventDisableTiming);
-    for (int i = 0; i < kFewSlabs && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&B.evStage[i], hipEventDisableTiming);
+    if (e == hipSuccess) e = new_event(B.evRecv, false);
+    for (int i = 0; i < kFewSlabs && e == hipSuccess; ++i) e = new_event(B.evStage[i], false);
     if (e != hipSuccess) return fail(YCNR_ERR_HIP, "set_ratings_banded: hipEventCreate: %s", hipGetErrorString(e));
     int r1 = upload_ratings(h, part.R, rows, cols, rowPtr, indx, vals, 0, rows, memKind, hp, "set_ratings_banded");
     if (r1) return r1;
     if (bpr <= 0 && part.R.nnz > 0) return fail(YCNR_ERR_INVALID, "set_ratings_banded: rank %d has no band but %lld ratings", rank, (long long)part.R.nnz);
     if (bpr > 0)
-      if (int r2 = check_index_bounds(part.R.dIndx, part.R.nnz, bandBounds[bl], bandBounds[bh], h->stream, "set_ratings_banded")) return r2;
+      if (int r2 = check_index_bounds(part.R.dIndx.get(), part.R.nnz, bandBounds[bl], bandBounds[bh], h->stream, "set_ratings_banded")) return r2;
     // where every row's ratings cross this rank's inner band boundaries (rows are sorted by column id)
     const int64_t base = hp[0];
     std::vector<int64_t> qRow, cuts;
@@ -1646,7 +1565,7 @@ int ycnr_als_set_ratings_banded(ycnr_als *h, int side, const int64_t *rowPtr, co
       if (hp[r + 1] != hp[r]) qRow.push_back(r);
     for (int b = bl + 1; b < bh; ++b) keys.push_back((int32_t)bandBounds[b]);
     const BoundQueries q = bound_queries(hp.data(), qRow, keys);
-    if (int r3 = lower_bound_i32(part.R.dIndx, q.beg, q.end, q.key, cuts, h->stream)) return r3;
+    if (int r3 = lower_bound_i32(part.R.dIndx.get(), q.beg, q.end, q.key, cuts, h->stream)) return r3;
     for (size_t i = 0; i < qRow.size(); ++i) {
       const int64_t r = qRow[i];
       int64_t p = hp[r] - base;
@@ -1698,28 +1617,28 @@ int ycnr_als_set_ratings_banded(ycnr_als *h, int side, const int64_t *rowPtr, co
     S.maxRowSlabs = nBands;
     B.ownedSolved = S.nSplit;
     if (S.nUnits) {
-      HIP_TRY(hipMalloc(&S.dUnits, sizeof(Unit) * plan.units.size()));
-      HIP_TRY(hipMemcpy(S.dUnits, plan.units.data(), sizeof(Unit) * plan.units.size(), hipMemcpyHostToDevice));
+      HIP_TRY(hipMalloc(S.dUnits.put(), sizeof(Unit) * plan.units.size()));
+      HIP_TRY(hipMemcpy(S.dUnits.get(), plan.units.data(), sizeof(Unit) * plan.units.size(), hipMemcpyHostToDevice));
     }
     if (B.nSums) {
-      HIP_TRY(hipMalloc(&B.dSums, sizeof(SlabSum) * plan.sums.size()));
-      HIP_TRY(hipMemcpy(B.dSums, plan.sums.data(), sizeof(SlabSum) * plan.sums.size(), hipMemcpyHostToDevice));
+      HIP_TRY(hipMalloc(B.dSums.put(), sizeof(SlabSum) * plan.sums.size()));
+      HIP_TRY(hipMemcpy(B.dSums.get(), plan.sums.data(), sizeof(SlabSum) * plan.sums.size(), hipMemcpyHostToDevice));
     }
     if (S.nSplit) {
-      HIP_TRY(hipMalloc(&S.dSplit, sizeof(SplitRow) * plan.owned.size()));
-      HIP_TRY(hipMemcpy(S.dSplit, plan.owned.data(), sizeof(SplitRow) * plan.owned.size(), hipMemcpyHostToDevice));
+      HIP_TRY(hipMalloc(S.dSplit.put(), sizeof(SplitRow) * plan.owned.size()));
+      HIP_TRY(hipMemcpy(S.dSplit.get(), plan.owned.data(), sizeof(SplitRow) * plan.owned.size(), hipMemcpyHostToDevice));
     }
     const size_t slabBytes = (size_t)B.slabElems * ts;
-    HIP_TRY(hipMalloc(&S.dSlabs, std::max<size_t>((size_t)(B.bandSlabs + B.tmpSlabs) * slabBytes, 64)));
-    HIP_TRY(hipMalloc(&B.dRecv, std::max<size_t>((size_t)B.recvSlabs * slabBytes, 64)));
-    HIP_TRY(hipMemset(B.dRecv, 0, std::max<size_t>((size_t)B.recvSlabs * slabBytes, 64)));
+    HIP_TRY(hipMalloc(S.dSlabs.put(), std::max<size_t>((size_t)(B.bandSlabs + B.tmpSlabs) * slabBytes, 64)));
+    HIP_TRY(hipMalloc(B.dRecv.put(), std::max<size_t>((size_t)B.recvSlabs * slabBytes, 64)));
+    HIP_TRY(hipMemset(B.dRecv.get(), 0, std::max<size_t>((size_t)B.recvSlabs * slabBytes, 64)));
     // the owners' table as pointers: a rank's own band slabs are in its arena, the other ranks' arrive in dRecv
     std::vector<const void *> table(plan.table.size(), nullptr);
     for (size_t i = 0; i < table.size(); ++i)
       if (plan.table[i].src >= 0)
-        table[i] = (const char *)(plan.table[i].src == rank ? S.dSlabs : B.dRecv) + (size_t)plan.table[i].slab * slabBytes;
-    HIP_TRY(hipMalloc((void **)&B.dTable, std::max<size_t>(sizeof(void *) * table.size(), 64)));
-    if (!table.empty()) HIP_TRY(hipMemcpy((void *)B.dTable, table.data(), sizeof(void *) * table.size(), hipMemcpyHostToDevice));
+        table[i] = (const char *)(plan.table[i].src == rank ? S.dSlabs.get() : B.dRecv.get()) + (size_t)plan.table[i].slab * slabBytes;
+    HIP_TRY(hipMalloc(B.dTable.put(), std::max<size_t>(sizeof(void *) * table.size(), 64)));
+    if (!table.empty()) HIP_TRY(hipMemcpy((void *)B.dTable.get(), table.data(), sizeof(void *) * table.size(), hipMemcpyHostToDevice));
     B.on = true;
     return YCNR_OK;
   };
@@ -1727,19 +1646,15 @@ int ycnr_als_set_ratings_banded(ycnr_als *h, int side, const int64_t *rowPtr, co
   // IPC: the peers push their band slabs into dRecv -- published here, collectively (a rank that failed says so in its slot)
   if (h->comm.active() && h->comm.transport == YCNR_COMM_IPC) {
     const std::string why = g_last_error;
-    const int rcp = ipc_publish_extra(h->comm, side, rc ? nullptr : B.dRecv, rc != YCNR_OK);
+    const int rcp = ipc_publish_extra(h->comm, side, rc ? nullptr : B.dRecv.get(), rc != YCNR_OK);
     if (rc) g_last_error = why;
     else rc = rcp;
   }
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(h->stream));
-  for (Part &p : h->parts[side]) p.release();
-  h->parts[side].clear();
-  h->banded[side].release();
   h->drop_graphs();
-  h->parts[side].push_back(part);
-  h->banded[side] = B;
-  pend.keep = true;
+  h->parts[side].swap(staged);  // the previous upload is freed as `staged` goes out of scope
+  h->banded[side] = std::move(B);
   // the solved rows travel like a sharded side's: one piece per rank (ycnr_als_exchange, the exchange behind the half-step)
   h->bounds[side].clear();
   for (int r = 0; r < world; ++r) {
@@ -1760,10 +1675,10 @@ int ycnr_als_set_rmse_ratings(ycnr_als *h, int which, const int64_t *rowPtr, con
   if (rc) return rc;
   const int64_t base = hp[0];
   for (auto &v : hp) v -= base;
-  hipError_t e = hipMalloc(&R.dRowPtr, sizeof(int64_t) * hp.size());
-  if (e == hipSuccess) e = hipMemcpy(R.dRowPtr, hp.data(), sizeof(int64_t) * hp.size(), hipMemcpyHostToDevice);
+  hipError_t e = hipMalloc(R.dRowPtr.put(), sizeof(int64_t) * hp.size());
+  if (e == hipSuccess) e = hipMemcpy(R.dRowPtr.get(), hp.data(), sizeof(int64_t) * hp.size(), hipMemcpyHostToDevice);
   if (e != hipSuccess) {
-    R.release();  // never "loaded" without its row pointers
+    R = Ratings();  // never "loaded" without its row pointers
     return fail(e == hipErrorOutOfMemory ? YCNR_ERR_NOMEM : YCNR_ERR_HIP, "set_rmse_ratings: %s", hipGetErrorString(e));
   }
   return YCNR_OK;
@@ -1811,10 +1726,9 @@ int ycnr_als_bind_factors(ycnr_als *h, int side, void *p) {
     return fail(YCNR_ERR_INVALID, "bind_factors: not a device pointer");
   }
   HIP_TRY(hipStreamSynchronize(h->stream));
-  if (h->ownFactors[side] && h->factors[side]) (void)hipFree(h->factors[side]);
+  h->factorsMem[side].reset();
   h->drop_graphs();
   h->factors[side] = p;
-  h->ownFactors[side] = false;
   return YCNR_OK;
 }
 
@@ -1828,16 +1742,18 @@ int ycnr_als_bind_factors(ycnr_als *h, int side, void *p) {
 static int launch_part(ycnr_als *h, int side, Part &part, hipStream_t stream, bool branches = false, bool inOrder = false) {
   const Ratings &R = part.R;
   const Schedule &S = part.S;
-  hipEvent_t *ev = branches ? nullptr : part.ev;
+  hipEvent_t evs[5];  // the raw view of the piece's timing events that the launch_* functions record
+  for (int i = 0; i < 5; ++i) evs[i] = part.ev[i].get();
+  hipEvent_t *ev = branches ? nullptr : evs;
   const StepShape shape = h->shape(side);
   const PathKind path = step_path(shape.f64, shape.k);
   if (h->copt.dtype == YCNR_F32) {
     // (copt.factorsCount = kPad when the matrices are padded)
-    StepArgs<float> a = h->kPad ? step_args<float>(h, side, part, h->padded[1 - side], h->padded[side])
+    StepArgs<float> a = h->kPad ? step_args<float>(h, side, part, h->padded[1 - side].get(), h->padded[side].get())
                                 : step_args<float>(h, side, part, h->factors[1 - side], h->factors[side]);
     if (h->kPad) a.kReal = h->opt.factorsCount;
     if (h->planes[1 - side] && h->planesValid[1 - side] && use_planes(shape, env_flags())) {
-      a.planes = h->planes[1 - side];
+      a.planes = h->planes[1 - side].get();
       a.planesBytes = (uint32_t)(h->rows(1 - side) * planes_row_bytes(slab_nb(h->copt.factorsCount), planes_pack(h->copt.factorsCount)));
     }
     DualPlan dp;
@@ -1853,22 +1769,22 @@ static int launch_part(ycnr_als *h, int side, Part &part, hipStream_t stream, bo
         // (a captured small half-step keeps two branches for its dual classes: every branch is a join, 30 - 60 us each)
         dp.nSide = branches ? std::min(2, side_streams()) : side_streams();
         for (int i = 0; i < dp.nSide; ++i) {
-          if (!h->sideStream[i]) HIP_TRY(hipStreamCreateWithFlags(&h->sideStream[i], hipStreamNonBlocking));
-          dp.side[i] = h->sideStream[i];
-          dp.join[i] = part.join[i];
+          if (!h->sideStream[i]) HIP_TRY(hipStreamCreateWithFlags(h->sideStream[i].put(), hipStreamNonBlocking));
+          dp.side[i] = h->sideStream[i].get();
+          dp.join[i] = part.join[i].get();
         }
       }
     }
-    dp.fork = part.fork;
+    dp.fork = part.fork.get();
     if (branches) {
-      dp.slabStream = h->pieceStream[0];
-      dp.slabJoin = part.slabJoin;
+      dp.slabStream = h->pieceStream[0].get();
+      dp.slabJoin = part.slabJoin.get();
     }
     int rc;
     if (path == kAnyK)
       rc = launch_step_gen<float>(a, S.genBatches, stream, ev, dp);
     else if (path == kWorkgroup)
-      rc = launch_step_big(a, S.nUnits, S.nSlabs, S.nSplit, stream, ev, dp, S.dRowSlabs, S.rowSlabRows);
+      rc = launch_step_big(a, S.nUnits, S.nSlabs, S.nSplit, stream, ev, dp, S.dRowSlabs.get(), S.rowSlabRows);
     else
       rc = launch_step<float>(a, S.nUnits, S.nSlabs, S.nSplit, stream, ev, (h->copt.flags & YCNR_FLAG_LDS_SOLVER) != 0, dp,
                               use_valu_edge(shape), use_slab_x6(shape));
@@ -1876,7 +1792,7 @@ static int launch_part(ycnr_als *h, int side, Part &part, hipStream_t stream, bo
     // the piece's solved rows back into the caller's matrix (before its exchange)
     const int64_t nr = R.rowEnd - R.rowBegin, n = nr * h->opt.factorsCount;
     if (n > 0) {
-      hipLaunchKernelGGL(unpad_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const float *)h->padded[side],
+      hipLaunchKernelGGL(unpad_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const float *)h->padded[side].get(),
                          (float *)h->factors[side], R.rowBegin, nr, h->opt.factorsCount, h->kPad);
       HIP_TRY(hipGetLastError());
     }
@@ -1885,10 +1801,10 @@ static int launch_part(ycnr_als *h, int side, Part &part, hipStream_t stream, bo
   const StepArgs<double> a = step_args<double>(h, side, part, h->factors[1 - side], h->factors[side]);
   if (path == kAnyK) return launch_step_gen<double>(a, S.genBatches, stream, ev, DualPlan());
   DualPlan dpd;  // float64 has no dual classes; the chunk branch of the small-upload form applies
-  dpd.fork = part.fork;
+  dpd.fork = part.fork.get();
   if (branches) {
-    dpd.slabStream = h->pieceStream[0];
-    dpd.slabJoin = part.slabJoin;
+    dpd.slabStream = h->pieceStream[0].get();
+    dpd.slabJoin = part.slabJoin.get();
   }
   return launch_step<double>(a, S.nUnits, S.nSlabs, S.nSplit, stream, ev, (h->copt.flags & YCNR_FLAG_LDS_SOLVER) != 0, dpd);
 }
@@ -1968,7 +1884,7 @@ static int step_banded_t(ycnr_als *h, int side) {
   RowKernels<T> rk;
   if (int rc = row_kernels<T>(a, (h->copt.flags & YCNR_FLAG_LDS_SOLVER) != 0, use_valu_edge(h->shape(side)), use_slab_x6(h->shape(side)), false, rk)) return rc;
   if (int rc = set_max_lds(reinterpret_cast<const void *>(rk.band), rk.ldsReduce)) return rc;
-  HIP_TRY(hipEventRecord(part.ev[0], stream));
+  HIP_TRY(hipEventRecord(part.ev[0].get(), stream));
   const int bpr = (int)(B.rankBands[(size_t)B.rank + 1] - B.rankBands[(size_t)B.rank]);
   // The groups are dealt over up to four streams (the handle's two piece streams and two of its side streams): a group is an
   // eighth of the rows -- about one round of waves -- and its longest chunk sets its kernel's length, so the kernels of several
@@ -1981,14 +1897,14 @@ static int step_banded_t(ycnr_als *h, int side) {
     nStreams = std::min(want, B.world);
     for (int i = 0; i < nStreams; ++i) {
       if (i < 2) {
-        gs[i] = h->pieceStream[i];
+        gs[i] = h->pieceStream[i].get();
       } else {
-        if (!h->sideStream[i - 2]) HIP_TRY(hipStreamCreateWithFlags(&h->sideStream[i - 2], hipStreamNonBlocking));
-        gs[i] = h->sideStream[i - 2];
+        if (!h->sideStream[i - 2]) HIP_TRY(hipStreamCreateWithFlags(h->sideStream[i - 2].put(), hipStreamNonBlocking));
+        gs[i] = h->sideStream[i - 2].get();
       }
     }
-    HIP_TRY(hipEventRecord(h->evStepStart, stream));
-    for (int i = 0; i < nStreams; ++i) HIP_TRY(hipStreamWaitEvent(gs[i], h->evStepStart, 0));
+    HIP_TRY(hipEventRecord(h->evStepStart.get(), stream));
+    for (int i = 0; i < nStreams; ++i) HIP_TRY(hipStreamWaitEvent(gs[i], h->evStepStart.get(), 0));
   }
   const bool twoStreams = nStreams > 1;
   // stages per launch: consecutive stages' units (and sums) are contiguous, one launch covers `batch` of them -- enough units to
@@ -2009,16 +1925,16 @@ static int step_banded_t(ycnr_als *h, int side) {
       if (nu > 0x7fffffffLL) return fail(YCNR_ERR_UNSUPPORTED, "too many work units for one launch (%lld)", (long long)nu);
       if (nu > 0) {
         StepArgs<T> ag = a;
-        ag.units = S.dUnits + B.groupUnit0[(size_t)g0];
+        ag.units = S.dUnits.get() + B.groupUnit0[(size_t)g0];
         hipLaunchKernelGGL(rk.chunk, dim3((unsigned)nu), dim3(64), 0, ps, ag);
         HIP_TRY(hipGetLastError());
       }
       if (ns > 0) {
-        hipLaunchKernelGGL(als_slab_sum_kernel<T>, dim3((unsigned)ns), dim3(256), 0, ps, (T *)S.dSlabs, (const SlabSum *)B.dSums + B.groupSum0[(size_t)g0], B.slabElems);
+        hipLaunchKernelGGL(als_slab_sum_kernel<T>, dim3((unsigned)ns), dim3(256), 0, ps, (T *)S.dSlabs.get(), (const SlabSum *)B.dSums.get() + B.groupSum0[(size_t)g0], B.slabElems);
         HIP_TRY(hipGetLastError());
       }
     }
-    HIP_TRY(hipEventRecord(B.evStage[s - 1], ps));
+    HIP_TRY(hipEventRecord(B.evStage[s - 1].get(), ps));
     if (!comm || g == B.rank) continue;
     const int from = (B.rank - s + B.world) % B.world;  // the rank whose stage-s group this rank is
     const int64_t sendSlabs = (B.ownerBounds[(size_t)g + 1] - B.ownerBounds[(size_t)g]) * bpr;
@@ -2026,14 +1942,14 @@ static int step_banded_t(ycnr_als *h, int side) {
     const int64_t recvSlabs = ownN * (B.rankBands[(size_t)from + 1] - B.rankBands[(size_t)from]);
     h->info.exchangeBytes += (sendSlabs + recvSlabs) * (int64_t)slabBytes;
     if (c.transport == YCNR_COMM_STUB) continue;  // (one rank of an emulated world: the bytes are counted, nothing travels)
-    HIP_TRY(hipStreamWaitEvent(c.stream, B.evStage[s - 1], 0));
-    const char *src = (const char *)S.dSlabs + (size_t)B.groupSlab0[(size_t)g] * slabBytes;
+    HIP_TRY(hipStreamWaitEvent(c.stream, B.evStage[s - 1].get(), 0));
+    const char *src = (const char *)S.dSlabs.get() + (size_t)B.groupSlab0[(size_t)g] * slabBytes;
     if (c.transport == YCNR_COMM_RCCL) {
       const ncclDataType_t dt = ts == 8 ? ncclDouble : ncclFloat;
       NCCL_TRY(c.api, c.api->GroupStart());
       if (sendSlabs > 0) NCCL_TRY(c.api, c.api->Send(src, (size_t)sendSlabs * (size_t)B.slabElems, dt, g, c.nccl, c.stream));
       if (recvSlabs > 0)
-        NCCL_TRY(c.api, c.api->Recv((char *)B.dRecv + (size_t)B.recvSlab0[(size_t)from] * slabBytes, (size_t)recvSlabs * (size_t)B.slabElems, dt, from, c.nccl, c.stream));
+        NCCL_TRY(c.api, c.api->Recv((char *)B.dRecv.get() + (size_t)B.recvSlab0[(size_t)from] * slabBytes, (size_t)recvSlabs * (size_t)B.slabElems, dt, from, c.nccl, c.stream));
       NCCL_TRY(c.api, c.api->GroupEnd());
     } else if (c.transport == YCNR_COMM_IPC) {
       if (c.extra[side].size() != (size_t)c.world || (sendSlabs > 0 && !c.extra[side][(size_t)g].ptr))
@@ -2052,22 +1968,22 @@ static int step_banded_t(ycnr_als *h, int side) {
   // the step's stream joins the piece streams: the last stage of each (enqueued behind every launch, as in ycnr_als_step_async)
   if (twoStreams) {
     const int nb = (B.world + batch - 1) / batch;  // the last launch of every stream in use
-    for (int bi = std::max(0, nb - nStreams); bi < nb; ++bi) HIP_TRY(hipStreamWaitEvent(stream, B.evStage[std::min(B.world, (bi + 1) * batch) - 1], 0));
+    for (int bi = std::max(0, nb - nStreams); bi < nb; ++bi) HIP_TRY(hipStreamWaitEvent(stream, B.evStage[std::min(B.world, (bi + 1) * batch) - 1].get(), 0));
   }
-  for (int i = 1; i <= 3; ++i) HIP_TRY(hipEventRecord(part.ev[i], stream));  // (no row kernel, no dual classes)
+  for (int i = 1; i <= 3; ++i) HIP_TRY(hipEventRecord(part.ev[i].get(), stream));  // (no row kernel, no dual classes)
   if (comm && c.transport == YCNR_COMM_RCCL) {
-    HIP_TRY(hipEventRecord(B.evRecv, c.stream));
-    HIP_TRY(hipStreamWaitEvent(stream, B.evRecv, 0));
+    HIP_TRY(hipEventRecord(B.evRecv.get(), c.stream));
+    HIP_TRY(hipStreamWaitEvent(stream, B.evRecv.get(), 0));
   } else if (comm && c.transport == YCNR_COMM_IPC) {
     HIP_TRY(hipStreamSynchronize(c.stream));  // this rank's pushes have landed ...
     if (int rcb = shm_barrier(c)) return rcb;  // ... and everybody's
   }
   if (S.nSplit > 0x7fffffffLL) return fail(YCNR_ERR_UNSUPPORTED, "too many split rows for one launch (%lld)", (long long)S.nSplit);
   if (S.nSplit > 0) {
-    hipLaunchKernelGGL(rk.band, dim3((unsigned)S.nSplit), dim3(64), rk.ldsReduce, stream, a, reinterpret_cast<const T *const *>(B.dTable), (int32_t)B.nBands);
+    hipLaunchKernelGGL(rk.band, dim3((unsigned)S.nSplit), dim3(64), rk.ldsReduce, stream, a, reinterpret_cast<const T *const *>(B.dTable.get()), (int32_t)B.nBands);
     HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(hipEventRecord(part.ev[4], stream));
+  HIP_TRY(hipEventRecord(part.ev[4].get(), stream));
   h->exchangedInStep = comm;
   if (comm) {
     std::vector<int64_t> xb((size_t)B.world), xe((size_t)B.world);
@@ -2075,12 +1991,12 @@ static int step_banded_t(ycnr_als *h, int side) {
       xb[(size_t)r] = B.ownerBounds[(size_t)r];
       xe[(size_t)r] = B.ownerBounds[(size_t)r + 1];
     }
-    int rc = comm_exchange(c, h->factors[side], side, h->opt.factorsCount, ts, xb.data(), xe.data(), stream, part.ready, part.x0, part.x1, &h->info.exchangeBytes);
+    int rc = comm_exchange(c, h->factors[side], side, h->opt.factorsCount, ts, xb.data(), xe.data(), stream, part.ready.get(), part.x0.get(), part.x1.get(), &h->info.exchangeBytes);
     if (rc) return rc;
-    HIP_TRY(hipEventRecord(h->evComputeEnd, stream));
-    if (c.transport != YCNR_COMM_SHM) HIP_TRY(hipStreamWaitEvent(stream, part.x1, 0));
+    HIP_TRY(hipEventRecord(h->evComputeEnd.get(), stream));
+    if (c.transport != YCNR_COMM_SHM) HIP_TRY(hipStreamWaitEvent(stream, part.x1.get(), 0));
   }
-  HIP_TRY(hipMemcpyAsync(h->hErr, h->dErr, sizeof(ErrInfo), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(h->hErr.get(), h->dErr.get(), sizeof(ErrInfo), hipMemcpyDeviceToHost, stream));
   return YCNR_OK;
 }
 
@@ -2129,13 +2045,13 @@ int ycnr_als_step_async(ycnr_als *h, int side) {
     const int s = 1 - side;
     const int64_t n = h->rows(s) * h->kPad;
     hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const float *)h->factors[s],
-                       h->padded[s], (int64_t)0, h->rows(s), h->opt.factorsCount, h->kPad);
+                       h->padded[s].get(), (int64_t)0, h->rows(s), h->opt.factorsCount, h->kPad);
     HIP_TRY(hipGetLastError());
     for (const Part &p : parts) {
       const int64_t nr = p.R.rowEnd - p.R.rowBegin, m = nr * h->kPad;
       if (m <= 0) continue;
       hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, h->stream, (const float *)h->factors[side],
-                         h->padded[side], p.R.rowBegin, nr, h->opt.factorsCount, h->kPad);
+                         h->padded[side].get(), p.R.rowBegin, nr, h->opt.factorsCount, h->kPad);
       HIP_TRY(hipGetLastError());
     }
   }
@@ -2153,13 +2069,13 @@ int ycnr_als_step_async(ycnr_als *h, int side) {
     const int s = 1 - side, nb = slab_nb(h->copt.factorsCount);
     const bool pack = planes_pack(h->copt.factorsCount);
     const int64_t n = h->rows(s) * nb * 4;
-    hipLaunchKernelGGL(als_split_planes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->kPad ? (const float *)h->padded[s] : (const float *)h->factors[s], h->planes[s],
+    hipLaunchKernelGGL(als_split_planes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->kPad ? (const float *)h->padded[s].get() : (const float *)h->factors[s], h->planes[s].get(),
                        h->rows(s), h->copt.factorsCount, nb, pack ? 1 : 0);
     HIP_TRY(hipGetLastError());
     return YCNR_OK;
   };
-  if (planesNow && !h->planes[1 - side])
-    HIP_TRY(hipMalloc(&h->planes[1 - side], (size_t)h->rows(1 - side) * (size_t)planes_row_bytes(slab_nb(h->copt.factorsCount), planes_pack(h->copt.factorsCount))));
+  if (planesNow && !h->planes[1 - side].get())
+    HIP_TRY(hipMalloc(h->planes[1 - side].put(), (size_t)h->rows(1 - side) * (size_t)planes_row_bytes(slab_nb(h->copt.factorsCount), planes_pack(h->copt.factorsCount))));
   memset(&h->info, 0, sizeof h->info);
   // Small uploads (the ML-100k / ML-1M shapes): ~15 launches, forks and joins of a half-step whose kernels each fill a
   // fraction of the chip.  Captured once in the branch form (launch_part) and replayed: one launch per half-step.
@@ -2167,16 +2083,16 @@ int ycnr_als_step_async(ycnr_als *h, int side) {
   {
     ycnr_als::GraphSlot &gs = h->graph[side];
     // (a padded upload -- kPad -- is captured too: the pads above are plain launches in front of the graph, the unpad of the piece's rows is part of it)
-    const bool graphable = ycnr::graphable(h->shape(side), env_flags(), exchange, parts.size(), parts[0].R.nnz, h->stream == h->ownStream);
+    const bool graphable = ycnr::graphable(h->shape(side), env_flags(), exchange, parts.size(), parts[0].R.nnz, h->stream == h->ownStream.get());
     if (graphable && gs.state == 1) {
       for (int i = 0; i < side_streams(); ++i)  // (not inside the capture)
-        if (!h->sideStream[i]) HIP_TRY(hipStreamCreateWithFlags(&h->sideStream[i], hipStreamNonBlocking));
+        if (!h->sideStream[i]) HIP_TRY(hipStreamCreateWithFlags(h->sideStream[i].put(), hipStreamNonBlocking));
       gs.state = -1;
       hipGraph_t g = nullptr;
       if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeRelaxed) == hipSuccess) {
         int rc = split_planes();
         if (rc == YCNR_OK) rc = launch_part(h, side, parts[0], h->stream, true);
-        hipError_t ce = hipMemcpyAsync(h->hErr, h->dErr, sizeof(ErrInfo), hipMemcpyDeviceToHost, h->stream);
+        hipError_t ce = hipMemcpyAsync(h->hErr.get(), h->dErr.get(), sizeof(ErrInfo), hipMemcpyDeviceToHost, h->stream);
         hipError_t ee = hipStreamEndCapture(h->stream, &g);
         if (rc == YCNR_OK && ce == hipSuccess && ee == hipSuccess && g && hipGraphInstantiate(&gs.exec, g, nullptr, nullptr, 0) == hipSuccess)
           gs.state = 2;
@@ -2188,9 +2104,9 @@ int ycnr_als_step_async(ycnr_als *h, int side) {
     }
     if (graphable && gs.state == 2) {
       Part &p = parts[0];
-      HIP_TRY(hipEventRecord(p.ev[0], h->stream));
+      HIP_TRY(hipEventRecord(p.ev[0].get(), h->stream));
       HIP_TRY(hipGraphLaunch(gs.exec, h->stream));
-      HIP_TRY(hipEventRecord(p.ev[4], h->stream));
+      HIP_TRY(hipEventRecord(p.ev[4].get(), h->stream));
       h->graphRun = true;
     }
   }
@@ -2202,33 +2118,33 @@ int ycnr_als_step_async(ycnr_als *h, int side) {
   const bool twoStreams = parts.size() > 1 && !(h->opt.flags & YCNR_FLAG_NO_OVERLAP) && !env_flags().noOverlap &&
                           !(exchange && h->comm.transport == YCNR_COMM_SHM);
   if (twoStreams) {
-    HIP_TRY(hipEventRecord(h->evStepStart, h->stream));
-    for (int i = 0; i < 2; ++i) HIP_TRY(hipStreamWaitEvent(h->pieceStream[i], h->evStepStart, 0));
+    HIP_TRY(hipEventRecord(h->evStepStart.get(), h->stream));
+    for (int i = 0; i < 2; ++i) HIP_TRY(hipStreamWaitEvent(h->pieceStream[i].get(), h->evStepStart.get(), 0));
   }
   for (size_t c = 0; c < parts.size() && !h->graphRun; ++c) {
-    hipStream_t ps = twoStreams ? h->pieceStream[c & 1] : h->stream;
+    hipStream_t ps = twoStreams ? h->pieceStream[c & 1].get() : h->stream;
     static const bool pieceSides = getenv("YCNR_PIECE_SIDE_STREAMS") != nullptr;  // A/B: round 3's form (side streams inside every piece)
     int rc = launch_part(h, side, parts[c], ps, false, twoStreams && !pieceSides);
     if (rc) return rc;
     if (exchange) {
       part_ranges(h, side, (int)c, xb, xe);
-      rc = comm_exchange(h->comm, h->factors[side], side, h->opt.factorsCount, h->ts(), xb.data(), xe.data(), ps, parts[c].ready,
-                         parts[c].x0, parts[c].x1, &h->info.exchangeBytes);
+      rc = comm_exchange(h->comm, h->factors[side], side, h->opt.factorsCount, h->ts(), xb.data(), xe.data(), ps, parts[c].ready.get(),
+                         parts[c].x0.get(), parts[c].x1.get(), &h->info.exchangeBytes);
       if (rc) return rc;
     }
-    if (twoStreams && c + 2 >= parts.size()) HIP_TRY(hipEventRecord(parts[c].done, ps));  // the last piece of each stream
+    if (twoStreams && c + 2 >= parts.size()) HIP_TRY(hipEventRecord(parts[c].done.get(), ps));  // the last piece of each stream
   }
   // ... joins the step's stream -- enqueued only now, behind every piece's launches: streams share hardware queues (the
   // runtime has 4 or 8 for all the streams of a process), a hardware queue is served in order, and a wait for piece c enqueued
   // on the step's stream BEFORE the launches of piece c + 1 held those launches back whenever the two streams shared a queue
   // (kernel trace of one GPU's eighth of the MAL-scale user side: the fourth piece started when the third had ended).
   if (twoStreams && !h->graphRun)
-    for (size_t c = parts.size() >= 2 ? parts.size() - 2 : 0; c < parts.size(); ++c) HIP_TRY(hipStreamWaitEvent(h->stream, parts[c].done, 0));
+    for (size_t c = parts.size() >= 2 ? parts.size() - 2 : 0; c < parts.size(); ++c) HIP_TRY(hipStreamWaitEvent(h->stream, parts[c].done.get(), 0));
   if (exchange) {
-    HIP_TRY(hipEventRecord(h->evComputeEnd, h->stream));
-    if (h->comm.transport != YCNR_COMM_SHM) HIP_TRY(hipStreamWaitEvent(h->stream, parts.back().x1, 0));  // (SHM is synchronous)
+    HIP_TRY(hipEventRecord(h->evComputeEnd.get(), h->stream));
+    if (h->comm.transport != YCNR_COMM_SHM) HIP_TRY(hipStreamWaitEvent(h->stream, parts.back().x1.get(), 0));  // (SHM is synchronous)
   }
-  if (!h->graphRun) HIP_TRY(hipMemcpyAsync(h->hErr, h->dErr, sizeof(ErrInfo), hipMemcpyDeviceToHost, h->stream));
+  if (!h->graphRun) HIP_TRY(hipMemcpyAsync(h->hErr.get(), h->dErr.get(), sizeof(ErrInfo), hipMemcpyDeviceToHost, h->stream));
   note_enqueued(h, side, parts);
   return YCNR_OK;
 }
@@ -2251,46 +2167,46 @@ int ycnr_als_sync(ycnr_als *h) {
     float ms = 0;
     if (h->graphRun && !parts.empty()) {
       // one interval for the whole half-step: chunks -> reduce, the row kernel and the dual classes ran as branches of one graph
-      HIP_TRY(hipEventElapsedTime(&ms, parts[0].ev[0], parts[0].ev[4]));
+      HIP_TRY(hipEventElapsedTime(&ms, parts[0].ev[0].get(), parts[0].ev[4].get()));
       h->info.gramSolveMs = ms;
       h->info.dualOverlapped = 1;
     }
     for (const Part &p : parts) {
       if (h->graphRun) break;
-      HIP_TRY(hipEventElapsedTime(&ms, p.ev[0], p.ev[1]));
+      HIP_TRY(hipEventElapsedTime(&ms, p.ev[0].get(), p.ev[1].get()));
       h->info.gramSlabMs += ms;
-      HIP_TRY(hipEventElapsedTime(&ms, p.ev[1], p.ev[2]));
+      HIP_TRY(hipEventElapsedTime(&ms, p.ev[1].get(), p.ev[2].get()));
       h->info.gramSolveMs += ms;
-      HIP_TRY(hipEventElapsedTime(&ms, p.ev[2], p.ev[3]));
+      HIP_TRY(hipEventElapsedTime(&ms, p.ev[2].get(), p.ev[3].get()));
       h->info.dualSolveMs += ms;
-      HIP_TRY(hipEventElapsedTime(&ms, p.ev[3], p.ev[4]));
+      HIP_TRY(hipEventElapsedTime(&ms, p.ev[3].get(), p.ev[4].get()));
       h->info.reduceSolveMs += ms;
       if (h->exchangedInStep) {
-        HIP_TRY(hipEventElapsedTime(&ms, p.x0, p.x1));
+        HIP_TRY(hipEventElapsedTime(&ms, p.x0.get(), p.x1.get()));
         h->info.exchangeMs += ms;
       }
     }
     if (!parts.empty()) {
       h->info.totalMs = 0;
       for (const Part &p : parts) {  // (pieces run two at a time: the last one need not end last)
-        HIP_TRY(hipEventElapsedTime(&ms, parts.front().ev[0], p.ev[4]));
+        HIP_TRY(hipEventElapsedTime(&ms, parts.front().ev[0].get(), p.ev[4].get()));
         h->info.totalMs = std::max(h->info.totalMs, ms);
       }
       if (h->exchangedInStep) {
         if (h->comm.transport != YCNR_COMM_SHM) {
           // what the step's stream still had to wait for after its own last kernel
-          HIP_TRY(hipEventElapsedTime(&ms, h->evComputeEnd, parts.back().x1));
+          HIP_TRY(hipEventElapsedTime(&ms, h->evComputeEnd.get(), parts.back().x1.get()));
           h->info.exposedExchangeMs = ms > 0 ? ms : 0;
         } else {
           h->info.exposedExchangeMs = h->info.exchangeMs;  // the staged stand-in blocks the stream
-          HIP_TRY(hipEventElapsedTime(&ms, parts.back().x0, parts.back().x1));
+          HIP_TRY(hipEventElapsedTime(&ms, parts.back().x0.get(), parts.back().x1.get()));
           h->info.totalMs -= h->info.exchangeMs - ms;  // kernels only (the last exchange lies behind the last kernel)
         }
       }
     }
     // (the error counter is cumulative and copied at the end of every half-step: with two half-steps in flight the rows
     // counted since the last sync are reported with the last one)
-    ErrInfo ei = *h->hErr;  // copied by the step's stream, which has drained
+    ErrInfo ei = *h->hErr.get();  // copied by the step's stream, which has drained
     ei.count = last ? ei.count - h->errSeen : 0;
     h->errSeen += ei.count;
     h->info.numericErrors = ei.count;
@@ -2298,7 +2214,7 @@ int ycnr_als_sync(ycnr_als *h) {
 #ifdef YCNR_WG_STAMPS
     if (const char *path = getenv("YCNR_DUMP_STAMPS")) {
       std::vector<unsigned char> buf(kErrBytes);
-      HIP_TRY(hipMemcpy(buf.data(), h->dErr, kErrBytes, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(buf.data(), h->dErr.get(), kErrBytes, hipMemcpyDeviceToHost));
       if (FILE *f = fopen(path, "wb")) {
         fwrite(buf.data(), 1, buf.size(), f);
         fclose(f);
@@ -2378,41 +2294,33 @@ int ycnr_als_rmse(ycnr_als *h, int which, double shift, int nPortions, const int
   }
   const int np = (int)pieceEnds.size();
   std::vector<double> part((size_t)3 * np);
-  int64_t *dEnds = nullptr;
-  double *dOut = nullptr;
-  HIP_TRY(hipMalloc(&dEnds, sizeof(int64_t) * np));
-  hipError_t e = hipMalloc(&dOut, sizeof(double) * 3 * np);
-  if (e == hipSuccess) e = hipMemcpyAsync(dEnds, pieceEnds.data(), sizeof(int64_t) * np, hipMemcpyHostToDevice, h->stream);
-  EvPair evp;  // the kernel alone (ycnr_als_last_rmse_ms)
-  if (e == hipSuccess) e = evp.create();
-  if (e == hipSuccess) e = hipEventRecord(evp.a, h->stream);
-  if (e == hipSuccess) {
-    if (h->opt.dtype == YCNR_F32) {
-      RmseArgs<float> a{R.dRowPtr, R.dIndx, (const float *)R.dVals, (const float *)h->factors[0],
-                        (const float *)h->factors[1], dEnds, dOut, shift, R.rowBegin, h->opt.factorsCount};
-      launch_rmse(a, np, h->stream);
-    } else {
-      RmseArgs<double> a{R.dRowPtr, R.dIndx, (const double *)R.dVals, (const double *)h->factors[0],
-                         (const double *)h->factors[1], dEnds, dOut, shift, R.rowBegin, h->opt.factorsCount};
-      launch_rmse(a, np, h->stream);
-    }
-    e = hipGetLastError();
+  DevPtr<int64_t> dEnds;
+  DevPtr<double> dOut;
+  Event ev0, ev1;  // the kernel alone (ycnr_als_last_rmse_ms)
+  HIP_TRY(hipMalloc(dEnds.put(), sizeof(int64_t) * np));
+  HIP_TRY(hipMalloc(dOut.put(), sizeof(double) * 3 * np));
+  HIP_TRY(hipMemcpyAsync(dEnds.get(), pieceEnds.data(), sizeof(int64_t) * np, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipEventCreate(ev0.put()));
+  HIP_TRY(hipEventCreate(ev1.put()));
+  HIP_TRY(hipEventRecord(ev0.get(), h->stream));
+  if (h->opt.dtype == YCNR_F32) {
+    RmseArgs<float> a{R.dRowPtr.get(), R.dIndx.get(), (const float *)R.dVals.get(), (const float *)h->factors[0],
+                      (const float *)h->factors[1], dEnds.get(), dOut.get(), shift, R.rowBegin, h->opt.factorsCount};
+    launch_rmse(a, np, h->stream);
+  } else {
+    RmseArgs<double> a{R.dRowPtr.get(), R.dIndx.get(), (const double *)R.dVals.get(), (const double *)h->factors[0],
+                       (const double *)h->factors[1], dEnds.get(), dOut.get(), shift, R.rowBegin, h->opt.factorsCount};
+    launch_rmse(a, np, h->stream);
   }
-  if (e == hipSuccess) e = hipEventRecord(evp.b, h->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(part.data(), dOut, sizeof(double) * 3 * np, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e == hipSuccess) {
-    float ms = 0;
-    h->lastRmseMs = hipEventElapsedTime(&ms, evp.a, evp.b) == hipSuccess ? (double)ms : -1.0;
-  }
-  if (e == hipSuccess) {
-    for (int i = 0; i < 3 * nPort; ++i) out[i] = 0.0;
-    for (int j = 0; j < np; ++j)
-      for (int t = 0; t < 3; ++t) out[3 * pieceOf[j] + t] += part[(size_t)3 * j + t];
-  }
-  if (dEnds) (void)hipFree(dEnds);
-  if (dOut) (void)hipFree(dOut);
-  if (e != hipSuccess) return fail(YCNR_ERR_HIP, "rmse: %s", hipGetErrorString(e));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(ev1.get(), h->stream));
+  HIP_TRY(hipMemcpyAsync(part.data(), dOut.get(), sizeof(double) * 3 * np, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  float ms = 0;
+  h->lastRmseMs = hipEventElapsedTime(&ms, ev0.get(), ev1.get()) == hipSuccess ? (double)ms : -1.0;
+  for (int i = 0; i < 3 * nPort; ++i) out[i] = 0.0;
+  for (int j = 0; j < np; ++j)
+    for (int t = 0; t < 3; ++t) out[3 * pieceOf[j] + t] += part[(size_t)3 * j + t];
   return YCNR_OK;
 }
 
@@ -2426,15 +2334,6 @@ int ycnr_als_last_rmse_ms(ycnr_als *h, double *ms) {
 // ---- top-N recommend from the handle's own matrices (recommend_kernels.hip.h) ----
 extern "C++" {
 namespace {
-int rec_reserve(ycnr_als::RecBuf &b, size_t bytes) {
-  if (bytes <= b.cap) return YCNR_OK;
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.cap = 0;
-  HIP_TRY(hipMalloc(&b.p, bytes));
-  b.cap = bytes;
-  return YCNR_OK;
-}
 constexpr int64_t kRecFusedBatch = 65536;  // users per launch of the fused kernel (bounds the partial lists)
 
 // one batch of the fused path: scores + per-workgroup lists, then the merge into the output layout
@@ -2442,13 +2341,13 @@ template <typename T>
 void launch_topn(ycnr_als *h, const void *users, int64_t u0, int64_t nb, unsigned yblk, size_t lds, double shift, double thr, int take, int limit) {
   const unsigned ublk = (unsigned)((nb + 15) / 16);
   hipLaunchKernelGGL(recommend_topn_kernel<T>, dim3(ublk, yblk), dim3(256), lds, h->stream, (const T *)users,
-                     (const int32_t *)h->rec[ycnr_als::REC_USER_IDS].p + u0, nb, (const T *)h->factors[YCNR_BY_ITEM], h->opt.totalItemsCount,
-                     (int)h->opt.factorsCount, shift, thr, (const int64_t *)h->rec[ycnr_als::REC_SKIP_PTR].p + u0,
-                     (const int32_t *)h->rec[ycnr_als::REC_SKIP].p, take, (double *)h->rec[ycnr_als::REC_PART_V].p,
-                     (int32_t *)h->rec[ycnr_als::REC_PART_I].p);
-  hipLaunchKernelGGL(recommend_topn_merge_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, h->stream, (const double *)h->rec[ycnr_als::REC_PART_V].p,
-                     (const int32_t *)h->rec[ycnr_als::REC_PART_I].p, nb, (int)yblk, take, limit, (int32_t *)h->rec[ycnr_als::REC_IDS].p + u0 * limit,
-                     (double *)h->rec[ycnr_als::REC_PRED].p + u0 * limit, (int32_t *)h->rec[ycnr_als::REC_CNT].p + u0);
+                     (const int32_t *)h->rec[ycnr_als::REC_USER_IDS].get() + u0, nb, (const T *)h->factors[YCNR_BY_ITEM], h->opt.totalItemsCount,
+                     (int)h->opt.factorsCount, shift, thr, (const int64_t *)h->rec[ycnr_als::REC_SKIP_PTR].get() + u0,
+                     (const int32_t *)h->rec[ycnr_als::REC_SKIP].get(), take, (double *)h->rec[ycnr_als::REC_PART_V].get(),
+                     (int32_t *)h->rec[ycnr_als::REC_PART_I].get());
+  hipLaunchKernelGGL(recommend_topn_merge_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, h->stream, (const double *)h->rec[ycnr_als::REC_PART_V].get(),
+                     (const int32_t *)h->rec[ycnr_als::REC_PART_I].get(), nb, (int)yblk, take, limit, (int32_t *)h->rec[ycnr_als::REC_IDS].get() + u0 * limit,
+                     (double *)h->rec[ycnr_als::REC_PRED].get() + u0 * limit, (int32_t *)h->rec[ycnr_als::REC_CNT].get() + u0);
 }
 
 // one batch of the score-matrix path: the kernels of ycnr_recommend_items on the gathered user rows
@@ -2457,11 +2356,11 @@ void launch_scores_select(ycnr_als *h, const void *users, int64_t u0, int64_t nb
   const int k = h->opt.factorsCount;
   const int64_t totalItems = h->opt.totalItemsCount;
   const size_t kp = (size_t)((k + 15) & ~15);
-  T *rows = (T *)h->rec[ycnr_als::REC_ROWS].p;
-  double *scores = (double *)h->rec[ycnr_als::REC_SCORES].p;
-  const int64_t *skipPtr = (const int64_t *)h->rec[ycnr_als::REC_SKIP_PTR].p + u0;
+  T *rows = (T *)h->rec[ycnr_als::REC_ROWS].get();
+  double *scores = (double *)h->rec[ycnr_als::REC_SCORES].get();
+  const int64_t *skipPtr = (const int64_t *)h->rec[ycnr_als::REC_SKIP_PTR].get() + u0;
   hipLaunchKernelGGL(gather_rows_kernel<T>, dim3((unsigned)((nb * k + 255) / 256)), dim3(256), 0, h->stream, (const T *)users,
-                     (const int32_t *)h->rec[ycnr_als::REC_USER_IDS].p + u0, nb, k, rows);
+                     (const int32_t *)h->rec[ycnr_als::REC_USER_IDS].get() + u0, nb, k, rows);
   const unsigned ublk = (unsigned)((nb + 15) / 16);
   const unsigned yblk = (unsigned)std::max<int64_t>(1, std::min<int64_t>((totalItems + 63) / 64, (8 * device_cus() + ublk - 1) / ublk));
   if (valu)
@@ -2471,11 +2370,11 @@ void launch_scores_select(ycnr_als *h, const void *users, int64_t u0, int64_t nb
     hipLaunchKernelGGL(recommend_scores_mfma_kernel<T>, dim3(ublk, yblk), dim3(256), 16 * kp * sizeof(T), h->stream, (const T *)rows, nb,
                        (const T *)h->factors[YCNR_BY_ITEM], totalItems, k, shift, minRating, scores);
   if (anySkip)
-    hipLaunchKernelGGL(recommend_skip_kernel, dim3((unsigned)nb), dim3(256), 0, h->stream, skipPtr, (const int32_t *)h->rec[ycnr_als::REC_SKIP].p, totalItems,
+    hipLaunchKernelGGL(recommend_skip_kernel, dim3((unsigned)nb), dim3(256), 0, h->stream, skipPtr, (const int32_t *)h->rec[ycnr_als::REC_SKIP].get(), totalItems,
                        scores);
   hipLaunchKernelGGL(recommend_select_kernel, dim3((unsigned)nb), dim3(256), 0, h->stream, scores, totalItems, take, limit,
-                     (int32_t *)h->rec[ycnr_als::REC_IDS].p + u0 * limit, (double *)h->rec[ycnr_als::REC_PRED].p + u0 * limit,
-                     (int32_t *)h->rec[ycnr_als::REC_CNT].p + u0);
+                     (int32_t *)h->rec[ycnr_als::REC_IDS].get() + u0 * limit, (double *)h->rec[ycnr_als::REC_PRED].get() + u0 * limit,
+                     (int32_t *)h->rec[ycnr_als::REC_CNT].get() + u0);
 }
 
 // The validated request of ycnr_als_recommend / ycnr_als_recommend_for_ratings on the handle's stream: top-N of the rows
@@ -2491,10 +2390,10 @@ int recommend_run(ycnr_als *h, const void *users, int64_t nUsers, const int32_t 
   const size_t ts = h->ts();
   const int take = limit - 1;  // lib/YcnrController.js:268-269
   HIP_TRY(hipSetDevice(h->opt.device));
-  for (hipEvent_t &ev : h->recEv)
-    if (!ev) HIP_TRY(hipEventCreate(&ev));
+  for (Event &ev : h->recEv)
+    if (!ev) HIP_TRY(hipEventCreate(ev.put()));
   if (take == 0) {  // the reference returns nothing; still ordered behind the half-steps in flight
-    if (started) HIP_TRY(hipEventRecord(h->recEv[1], h->stream));
+    if (started) HIP_TRY(hipEventRecord(h->recEv[1].get(), h->stream));
     if (beforeSync)
       if (int rc = beforeSync()) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -2506,7 +2405,7 @@ int recommend_run(ycnr_als *h, const void *users, int64_t nUsers, const int32_t 
     if (deviceMs) *deviceMs = 0.0;
     if (deviceMs && started) {
       float ms = 0;
-      HIP_TRY(hipEventElapsedTime(&ms, h->recEv[0], h->recEv[1]));
+      HIP_TRY(hipEventElapsedTime(&ms, h->recEv[0].get(), h->recEv[1].get()));
       *deviceMs = ms;
     }
     return YCNR_OK;
@@ -2518,12 +2417,12 @@ int recommend_run(ycnr_als *h, const void *users, int64_t nUsers, const int32_t 
   const bool valu = getenv("YCNR_RECOMMEND_VALU") != nullptr || 16 * kp * ts > 48 * 1024;
   const bool fused = !valu && take <= kTopMaxTake;
   typedef ycnr_als A;
-  if (int rc = rec_reserve(h->rec[A::REC_USER_IDS], (size_t)nUsers * 4)) return rc;
-  if (int rc = rec_reserve(h->rec[A::REC_SKIP_PTR], (size_t)(nUsers + 1) * 8)) return rc;
-  if (int rc = rec_reserve(h->rec[A::REC_SKIP], std::max<size_t>((size_t)nSkip * 4, 8))) return rc;
-  if (int rc = rec_reserve(h->rec[A::REC_IDS], (size_t)nUsers * limit * 4)) return rc;
-  if (int rc = rec_reserve(h->rec[A::REC_PRED], (size_t)nUsers * limit * 8)) return rc;
-  if (int rc = rec_reserve(h->rec[A::REC_CNT], (size_t)nUsers * 4)) return rc;
+  HIP_TRY(h->rec[A::REC_USER_IDS].reserve((size_t)nUsers * 4));
+  HIP_TRY(h->rec[A::REC_SKIP_PTR].reserve((size_t)(nUsers + 1) * 8));
+  HIP_TRY(h->rec[A::REC_SKIP].reserve(std::max<size_t>((size_t)nSkip * 4, 8)));
+  HIP_TRY(h->rec[A::REC_IDS].reserve((size_t)nUsers * limit * 4));
+  HIP_TRY(h->rec[A::REC_PRED].reserve((size_t)nUsers * limit * 8));
+  HIP_TRY(h->rec[A::REC_CNT].reserve((size_t)nUsers * 4));
   // the item range of a user tile over enough workgroups to fill the chip four times, at least 16 tiles (4 per wave) each
   const int64_t ntiles = (totalItems + 15) / 16;
   auto parts_of = [&](int64_t nb) {
@@ -2535,22 +2434,22 @@ int recommend_run(ycnr_als *h, const void *users, int64_t nUsers, const int32_t 
   if (fused) {
     const int64_t last = nUsers % batch ? nUsers % batch : batch;
     const size_t lists = (size_t)std::max(batch * parts_of(batch), last * parts_of(last));
-    if (int rc = rec_reserve(h->rec[A::REC_PART_V], lists * take * 8)) return rc;
-    if (int rc = rec_reserve(h->rec[A::REC_PART_I], lists * take * 4)) return rc;
+    HIP_TRY(h->rec[A::REC_PART_V].reserve(lists * take * 8));
+    HIP_TRY(h->rec[A::REC_PART_I].reserve(lists * take * 4));
   } else {
-    if (int rc = rec_reserve(h->rec[A::REC_ROWS], (size_t)batch * k * ts)) return rc;
-    if (int rc = rec_reserve(h->rec[A::REC_SCORES], (size_t)batch * totalItems * 8)) return rc;
+    HIP_TRY(h->rec[A::REC_ROWS].reserve((size_t)batch * k * ts));
+    HIP_TRY(h->rec[A::REC_SCORES].reserve((size_t)batch * totalItems * 8));
   }
   // everything below is enqueued on the handle's stream: behind the half-steps in flight, like ycnr_als_rmse
   if (userIds) {
-    HIP_TRY(hipMemcpyAsync(h->rec[A::REC_USER_IDS].p, userIds, (size_t)nUsers * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->rec[A::REC_USER_IDS].get(), userIds, (size_t)nUsers * 4, hipMemcpyHostToDevice, h->stream));
   } else {
-    hipLaunchKernelGGL(foldin_iota_kernel, dim3((unsigned)((nUsers + 255) / 256)), dim3(256), 0, h->stream, (int32_t *)h->rec[A::REC_USER_IDS].p, nUsers);
+    hipLaunchKernelGGL(foldin_iota_kernel, dim3((unsigned)((nUsers + 255) / 256)), dim3(256), 0, h->stream, (int32_t *)h->rec[A::REC_USER_IDS].get(), nUsers);
     HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(hipMemcpyAsync(h->rec[A::REC_SKIP_PTR].p, skipPtr, (size_t)(nUsers + 1) * 8, hipMemcpyHostToDevice, h->stream));
-  if (nSkip) HIP_TRY(hipMemcpyAsync(h->rec[A::REC_SKIP].p, skipIds, (size_t)nSkip * 4, hipMemcpyHostToDevice, h->stream));
-  if (!started) HIP_TRY(hipEventRecord(h->recEv[0], h->stream));
+  HIP_TRY(hipMemcpyAsync(h->rec[A::REC_SKIP_PTR].get(), skipPtr, (size_t)(nUsers + 1) * 8, hipMemcpyHostToDevice, h->stream));
+  if (nSkip) HIP_TRY(hipMemcpyAsync(h->rec[A::REC_SKIP].get(), skipIds, (size_t)nSkip * 4, hipMemcpyHostToDevice, h->stream));
+  if (!started) HIP_TRY(hipEventRecord(h->recEv[0].get(), h->stream));
   const double thr = minRecommendRating < -DBL_MAX ? -DBL_MAX : minRecommendRating;  // (-inf is "out" in the score matrix: it never competes)
   const size_t lds = std::max<size_t>(16 * kp * ts, (size_t)64 * take * 12);
   for (int64_t u0 = 0; u0 < nUsers; u0 += batch) {
@@ -2567,19 +2466,19 @@ int recommend_run(ycnr_als *h, const void *users, int64_t nUsers, const int32_t 
   }
   if (dStatus) {
     hipLaunchKernelGGL(foldin_clear_lists_kernel, dim3((unsigned)((nUsers * limit + 255) / 256)), dim3(256), 0, h->stream, dStatus, nUsers, (int)limit,
-                       (int32_t *)h->rec[A::REC_IDS].p, (double *)h->rec[A::REC_PRED].p, (int32_t *)h->rec[A::REC_CNT].p);
+                       (int32_t *)h->rec[A::REC_IDS].get(), (double *)h->rec[A::REC_PRED].get(), (int32_t *)h->rec[A::REC_CNT].get());
     HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(hipEventRecord(h->recEv[1], h->stream));
-  HIP_TRY(hipMemcpyAsync(outIds, h->rec[A::REC_IDS].p, (size_t)nUsers * limit * 4, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipMemcpyAsync(outPredict, h->rec[A::REC_PRED].p, (size_t)nUsers * limit * 8, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipMemcpyAsync(outCount, h->rec[A::REC_CNT].p, (size_t)nUsers * 4, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipEventRecord(h->recEv[1].get(), h->stream));
+  HIP_TRY(hipMemcpyAsync(outIds, h->rec[A::REC_IDS].get(), (size_t)nUsers * limit * 4, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(outPredict, h->rec[A::REC_PRED].get(), (size_t)nUsers * limit * 8, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(outCount, h->rec[A::REC_CNT].get(), (size_t)nUsers * 4, hipMemcpyDeviceToHost, h->stream));
   if (beforeSync)
     if (int rc = beforeSync()) return rc;
   HIP_TRY(hipStreamSynchronize(h->stream));
   if (deviceMs) {
     float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, h->recEv[0], h->recEv[1]));
+    HIP_TRY(hipEventElapsedTime(&ms, h->recEv[0].get(), h->recEv[1].get()));
     *deviceMs = ms;
   }
   return YCNR_OK;
@@ -2631,18 +2530,18 @@ int fold_launch_steps(ycnr_als *h, int side, int64_t nRows, const int64_t *rowPt
   const size_t slabElems = (size_t)step_slab_elems(P.kind, k);
   h->foldPlan = plan_piece(rowPtr, 0, nRows, P);  // (kept on the handle: its lists are the source of the copies below)
   const PiecePlan &plan = h->foldPlan;
-  if (int rc = rec_reserve(h->rec[A::FOLD_UNITS], sizeof(Unit) * std::max<size_t>(1, plan.units.size()))) return rc;
-  if (int rc = rec_reserve(h->rec[A::FOLD_SPLIT], sizeof(SplitRow) * std::max<size_t>(1, plan.split.size()))) return rc;
-  if (int rc = rec_reserve(h->rec[A::FOLD_SLABS], sizeof(T) * std::max<size_t>(1, (size_t)plan.arenaSlabs * slabElems))) return rc;
-  if (int rc = rec_reserve(h->rec[A::FOLD_ERR], sizeof(ErrInfo))) return rc;
+  HIP_TRY(h->rec[A::FOLD_UNITS].reserve(sizeof(Unit) * std::max<size_t>(1, plan.units.size())));
+  HIP_TRY(h->rec[A::FOLD_SPLIT].reserve(sizeof(SplitRow) * std::max<size_t>(1, plan.split.size())));
+  HIP_TRY(h->rec[A::FOLD_SLABS].reserve(sizeof(T) * std::max<size_t>(1, (size_t)plan.arenaSlabs * slabElems)));
+  HIP_TRY(h->rec[A::FOLD_ERR].reserve(sizeof(ErrInfo)));
   if (!plan.units.empty())
-    HIP_TRY(hipMemcpyAsync(h->rec[A::FOLD_UNITS].p, plan.units.data(), sizeof(Unit) * plan.units.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->rec[A::FOLD_UNITS].get(), plan.units.data(), sizeof(Unit) * plan.units.size(), hipMemcpyHostToDevice, h->stream));
   if (!plan.split.empty())
-    HIP_TRY(hipMemcpyAsync(h->rec[A::FOLD_SPLIT].p, plan.split.data(), sizeof(SplitRow) * plan.split.size(), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemsetAsync(h->rec[A::FOLD_ERR].p, 0, sizeof(ErrInfo), h->stream));
-  StepArgs<T> a{(const Unit *)h->rec[A::FOLD_UNITS].p, (const SplitRow *)h->rec[A::FOLD_SPLIT].p, (const int32_t *)h->rec[A::FOLD_INDX].p,
-                (const T *)h->rec[A::FOLD_VALS].p, (const T *)h->factors[1 - side], (const T *)h->dZeros, (T *)h->rec[A::FOLD_ROWS].p,
-                (T *)h->rec[A::FOLD_SLABS].p, (ErrInfo *)h->rec[A::FOLD_ERR].p, lambda, k, 0, 0, 0u};
+    HIP_TRY(hipMemcpyAsync(h->rec[A::FOLD_SPLIT].get(), plan.split.data(), sizeof(SplitRow) * plan.split.size(), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemsetAsync(h->rec[A::FOLD_ERR].get(), 0, sizeof(ErrInfo), h->stream));
+  StepArgs<T> a{(const Unit *)h->rec[A::FOLD_UNITS].get(), (const SplitRow *)h->rec[A::FOLD_SPLIT].get(), (const int32_t *)h->rec[A::FOLD_INDX].get(),
+                (const T *)h->rec[A::FOLD_VALS].get(), (const T *)h->factors[1 - side], (const T *)h->dZeros.get(), (T *)h->rec[A::FOLD_ROWS].get(),
+                (T *)h->rec[A::FOLD_SLABS].get(), (ErrInfo *)h->rec[A::FOLD_ERR].get(), lambda, k, 0, 0, 0u};
   return launch_out_of_place<T>(a, plan, h->stream);
 }
 
@@ -2654,28 +2553,28 @@ int fold_enqueue(ycnr_als *h, int side, int64_t nRows, const int64_t *rowPtr, co
   const int k = h->opt.factorsCount;
   const int64_t total = rowPtr[nRows];
   const double lambda = side == YCNR_BY_USER ? h->opt.userFactReg : h->opt.itemFactReg;
-  if (int rc = rec_reserve(h->rec[A::FOLD_PTR], (size_t)(nRows + 1) * 8)) return rc;
-  if (int rc = rec_reserve(h->rec[A::FOLD_INDX], std::max<size_t>((size_t)total * 4 + 64, 8))) return rc;
-  if (int rc = rec_reserve(h->rec[A::FOLD_VALS], std::max<size_t>((size_t)total * sizeof(T) + 64, 8))) return rc;
-  if (int rc = rec_reserve(h->rec[A::FOLD_ROWS], (size_t)nRows * k * sizeof(T))) return rc;
-  if (int rc = rec_reserve(h->rec[A::FOLD_STATUS], (size_t)nRows * 4)) return rc;
+  HIP_TRY(h->rec[A::FOLD_PTR].reserve((size_t)(nRows + 1) * 8));
+  HIP_TRY(h->rec[A::FOLD_INDX].reserve(std::max<size_t>((size_t)total * 4 + 64, 8)));
+  HIP_TRY(h->rec[A::FOLD_VALS].reserve(std::max<size_t>((size_t)total * sizeof(T) + 64, 8)));
+  HIP_TRY(h->rec[A::FOLD_ROWS].reserve((size_t)nRows * k * sizeof(T)));
+  HIP_TRY(h->rec[A::FOLD_STATUS].reserve((size_t)nRows * 4));
   if (storeIds)
-    if (int rc = rec_reserve(h->rec[A::FOLD_STORE], (size_t)nRows * 4)) return rc;
-  for (hipEvent_t &ev : h->recEv)
-    if (!ev) HIP_TRY(hipEventCreate(&ev));
+    HIP_TRY(h->rec[A::FOLD_STORE].reserve((size_t)nRows * 4));
+  for (Event &ev : h->recEv)
+    if (!ev) HIP_TRY(hipEventCreate(ev.put()));
   // everything below is enqueued on the handle's stream: behind the half-steps in flight, like ycnr_als_rmse
-  HIP_TRY(hipMemcpyAsync(h->rec[A::FOLD_PTR].p, rowPtr, (size_t)(nRows + 1) * 8, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(h->rec[A::FOLD_PTR].get(), rowPtr, (size_t)(nRows + 1) * 8, hipMemcpyHostToDevice, h->stream));
   if (total) {
-    HIP_TRY(hipMemcpyAsync(h->rec[A::FOLD_INDX].p, indx, (size_t)total * 4, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->rec[A::FOLD_VALS].p, vals, (size_t)total * sizeof(T), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->rec[A::FOLD_INDX].get(), indx, (size_t)total * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->rec[A::FOLD_VALS].get(), vals, (size_t)total * sizeof(T), hipMemcpyHostToDevice, h->stream));
   }
-  if (storeIds) HIP_TRY(hipMemcpyAsync(h->rec[A::FOLD_STORE].p, storeIds, (size_t)nRows * 4, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipEventRecord(h->recEv[0], h->stream));
+  if (storeIds) HIP_TRY(hipMemcpyAsync(h->rec[A::FOLD_STORE].get(), storeIds, (size_t)nRows * 4, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipEventRecord(h->recEv[0].get(), h->stream));
   T *store = storeIds ? (T *)h->factors[side] : nullptr;
   if (k <= kFoldMaxK) {
-    FoldArgs<T> fa{(const int64_t *)h->rec[A::FOLD_PTR].p, (const int32_t *)h->rec[A::FOLD_INDX].p, (const T *)h->rec[A::FOLD_VALS].p,
-                   (const T *)h->factors[1 - side], (T *)h->rec[A::FOLD_ROWS].p, (int32_t *)h->rec[A::FOLD_STATUS].p, store,
-                   (const int32_t *)h->rec[A::FOLD_STORE].p, lambda, k};
+    FoldArgs<T> fa{(const int64_t *)h->rec[A::FOLD_PTR].get(), (const int32_t *)h->rec[A::FOLD_INDX].get(), (const T *)h->rec[A::FOLD_VALS].get(),
+                   (const T *)h->factors[1 - side], (T *)h->rec[A::FOLD_ROWS].get(), (int32_t *)h->rec[A::FOLD_STATUS].get(), store,
+                   (const int32_t *)h->rec[A::FOLD_STORE].get(), lambda, k};
     const size_t lds = foldin_lds_bytes(k);
     if (int rc = set_max_lds(reinterpret_cast<const void *>(als_foldin_kernel<T>), lds)) return rc;
     hipLaunchKernelGGL(als_foldin_kernel<T>, dim3((unsigned)nRows), dim3(256), lds, h->stream, fa);
@@ -2685,12 +2584,12 @@ int fold_enqueue(ycnr_als *h, int side, int64_t nRows, const int64_t *rowPtr, co
   if (total > 0)
     if (int rc = fold_launch_steps<T>(h, side, nRows, rowPtr, lambda)) return rc;
   if (total == 0) {
-    if (int rc = rec_reserve(h->rec[A::FOLD_ERR], sizeof(ErrInfo))) return rc;
-    HIP_TRY(hipMemsetAsync(h->rec[A::FOLD_ERR].p, 0, sizeof(ErrInfo), h->stream));
+    HIP_TRY(h->rec[A::FOLD_ERR].reserve(sizeof(ErrInfo)));
+    HIP_TRY(hipMemsetAsync(h->rec[A::FOLD_ERR].get(), 0, sizeof(ErrInfo), h->stream));
   }
-  hipLaunchKernelGGL(foldin_finish_kernel<T>, dim3((unsigned)nRows), dim3(256), 0, h->stream, (const int64_t *)h->rec[A::FOLD_PTR].p,
-                     (const ErrInfo *)h->rec[A::FOLD_ERR].p, nRows, k, (T *)h->rec[A::FOLD_ROWS].p, (int32_t *)h->rec[A::FOLD_STATUS].p, store,
-                     (const int32_t *)h->rec[A::FOLD_STORE].p);
+  hipLaunchKernelGGL(foldin_finish_kernel<T>, dim3((unsigned)nRows), dim3(256), 0, h->stream, (const int64_t *)h->rec[A::FOLD_PTR].get(),
+                     (const ErrInfo *)h->rec[A::FOLD_ERR].get(), nRows, k, (T *)h->rec[A::FOLD_ROWS].get(), (int32_t *)h->rec[A::FOLD_STATUS].get(), store,
+                     (const int32_t *)h->rec[A::FOLD_STORE].get());
   HIP_TRY(hipGetLastError());
   return YCNR_OK;
 }
@@ -2734,13 +2633,13 @@ int ycnr_als_fold_in(ycnr_als *h, int side, int64_t nRows, const int64_t *rowPtr
   HIP_TRY(hipSetDevice(h->opt.device));
   if (int rc = fold_enqueue_any(h, side, nRows, rowPtr, indx, vals, storeIds)) return rc;
   typedef ycnr_als A;
-  HIP_TRY(hipEventRecord(h->recEv[1], h->stream));
-  HIP_TRY(hipMemcpyAsync(outRows, h->rec[A::FOLD_ROWS].p, (size_t)nRows * h->opt.factorsCount * h->ts(), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipMemcpyAsync(outStatus, h->rec[A::FOLD_STATUS].p, (size_t)nRows * 4, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipEventRecord(h->recEv[1].get(), h->stream));
+  HIP_TRY(hipMemcpyAsync(outRows, h->rec[A::FOLD_ROWS].get(), (size_t)nRows * h->opt.factorsCount * h->ts(), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(outStatus, h->rec[A::FOLD_STATUS].get(), (size_t)nRows * 4, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   if (deviceMs) {
     float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, h->recEv[0], h->recEv[1]));
+    HIP_TRY(hipEventElapsedTime(&ms, h->recEv[0].get(), h->recEv[1].get()));
     *deviceMs = ms;
   }
   return YCNR_OK;
@@ -2765,12 +2664,12 @@ int ycnr_als_recommend_for_ratings(ycnr_als *h, int64_t nUsers, const int64_t *r
   const size_t rowBytes = (size_t)nUsers * h->opt.factorsCount * h->ts();
   // the solved rows never leave the device between the two halves; their copy to the host rides behind the top-N
   auto copies = [&]() -> int {
-    if (outRows) HIP_TRY(hipMemcpyAsync(outRows, h->rec[A::FOLD_ROWS].p, rowBytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(outStatus, h->rec[A::FOLD_STATUS].p, (size_t)nUsers * 4, hipMemcpyDeviceToHost, h->stream));
+    if (outRows) HIP_TRY(hipMemcpyAsync(outRows, h->rec[A::FOLD_ROWS].get(), rowBytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(outStatus, h->rec[A::FOLD_STATUS].get(), (size_t)nUsers * 4, hipMemcpyDeviceToHost, h->stream));
     return YCNR_OK;
   };
-  return recommend_run(h, h->rec[A::FOLD_ROWS].p, nUsers, nullptr, skipPtr, skipIds, globalAvgShift, minRecommendRating, limit, outIds, outPredict,
-                       outCount, deviceMs, true, (const int32_t *)h->rec[A::FOLD_STATUS].p, copies);
+  return recommend_run(h, h->rec[A::FOLD_ROWS].get(), nUsers, nullptr, skipPtr, skipIds, globalAvgShift, minRecommendRating, limit, outIds, outPredict,
+                       outCount, deviceMs, true, (const int32_t *)h->rec[A::FOLD_STATUS].get(), copies);
 }
 
 // ---- multi-GPU exchange (comm_impl.hip.h) ----
@@ -2859,7 +2758,7 @@ int ycnr_als_exchange(ycnr_als *h, int side) {
   }
   Part &p0 = h->parts[side][0];
   if (int rcb = ipc_enter(h->comm)) return rcb;
-  int rc = comm_exchange(h->comm, h->factors[side], side, h->opt.factorsCount, h->ts(), b.data(), e.data(), h->stream, p0.ready, p0.x0, p0.x1, nullptr);
+  int rc = comm_exchange(h->comm, h->factors[side], side, h->opt.factorsCount, h->ts(), b.data(), e.data(), h->stream, p0.ready.get(), p0.x0.get(), p0.x1.get(), nullptr);
   if (rc) return rc;
   if (h->comm.transport != YCNR_COMM_SHM) HIP_TRY(hipStreamSynchronize(h->comm.stream));
   return ipc_finish(h->comm);
@@ -2890,17 +2789,17 @@ int ycnr_als_comm_selftest(ycnr_als *h, int64_t nFloats) {
   for (int64_t i = 0; i < nFloats; ++i) src[(size_t)i] = (float)((i * 2654435761u) % 65521) + 0.25f * (float)c.rank;
   double sum[3] = {1.0 + c.rank, 2.0, -0.5 * c.rank};
   if (c.transport == YCNR_COMM_RCCL) {
-    DevBuf a, b;
-    HIP_TRY(hipMalloc(&a.p, sizeof(float) * (size_t)nFloats));
-    HIP_TRY(hipMalloc(&b.p, sizeof(float) * (size_t)nFloats));
-    HIP_TRY(hipMemcpy(a.p, src.data(), sizeof(float) * (size_t)nFloats, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(b.p, 0, sizeof(float) * (size_t)nFloats));
+    DevPtr<void> a, b;
+    HIP_TRY(hipMalloc(a.put(), sizeof(float) * (size_t)nFloats));
+    HIP_TRY(hipMalloc(b.put(), sizeof(float) * (size_t)nFloats));
+    HIP_TRY(hipMemcpy(a.get(), src.data(), sizeof(float) * (size_t)nFloats, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(b.get(), 0, sizeof(float) * (size_t)nFloats));
     NCCL_TRY(c.api, c.api->GroupStart());
-    NCCL_TRY(c.api, c.api->Send(a.p, (size_t)nFloats, ncclFloat, c.rank, c.nccl, c.stream));
-    NCCL_TRY(c.api, c.api->Recv(b.p, (size_t)nFloats, ncclFloat, c.rank, c.nccl, c.stream));
+    NCCL_TRY(c.api, c.api->Send(a.get(), (size_t)nFloats, ncclFloat, c.rank, c.nccl, c.stream));
+    NCCL_TRY(c.api, c.api->Recv(b.get(), (size_t)nFloats, ncclFloat, c.rank, c.nccl, c.stream));
     NCCL_TRY(c.api, c.api->GroupEnd());
     HIP_TRY(hipStreamSynchronize(c.stream));
-    HIP_TRY(hipMemcpy(got.data(), b.p, sizeof(float) * (size_t)nFloats, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(got.data(), b.get(), sizeof(float) * (size_t)nFloats, hipMemcpyDeviceToHost));
     if (memcmp(got.data(), src.data(), sizeof(float) * (size_t)nFloats) != 0)
       return fail(YCNR_ERR_STATE, "comm_selftest: the self-addressed ncclSend / ncclRecv pair did not return the bytes sent");
   }
@@ -2922,62 +2821,24 @@ namespace {
 // Per-thread state of the level-1 portion ops: the reference calls mw_calcTrainAlsPortion ~11 500
 // times per MAL half-step (EmfBase.js:99-103: 10 000 ratings per portion), so stream, device
 // buffers and -- when the host pins it -- the fixed factor matrix stay alive between calls.
-struct DevArena {
-  void *p = nullptr;
-  size_t cap = 0;
-  hipError_t reserve(size_t bytes) {
-    if (bytes <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    const size_t want = std::max<size_t>(bytes + bytes / 2, 4096);
-    hipError_t e = hipMalloc(&p, want);
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
-
-struct L1Ctx {
+struct L1State {
   int device = -1;
-  hipStream_t stream = nullptr;
-  DevArena io, slabs, misc;  // io: [solved | ErrInfo | units | split | indx | vals | compacted fixed rows]; misc: zero row
+  Stream stream;
+  GrowBuf<ArenaAlloc> io, slabs, misc;  // io: [solved | ErrInfo | units | split | indx | vals | compacted fixed rows]; misc: zero row
   // page-locked host image of io: ONE copy in (everything behind the solved rows) and ONE copy out (solved rows +
   // ErrInfo) per portion instead of five pageable copies, two memsets and two copies back
-  void *hostIo = nullptr;
-  size_t hostIoCap = 0;
-  hipError_t reserve_host(size_t bytes) {
-    if (bytes <= hostIoCap) return hipSuccess;
-    if (hostIo) (void)hipHostFree(hostIo);
-    hostIo = nullptr;
-    hostIoCap = 0;
-    const size_t cap = bytes + bytes / 2;
-    hipError_t e = hipHostMalloc(&hostIo, cap, hipHostMallocDefault);
-    if (e == hipSuccess) hostIoCap = cap;
-    return e;
-  }
+  GrowBuf<PinnedAlloc> hostIo;
   // fixed matrix pinned by ycnr_{s,d}AlsPinFixedFactors
   const void *pinnedHost = nullptr;
   int64_t pinnedRows = 0;
   int pinnedK = 0, pinnedDtype = -1;
-  DevArena pinned;
-  void release() {
+  GrowBuf<ArenaAlloc> pinned;
+};
+struct L1Ctx : L1State {
+  void release() {  // on the state's device, with its stream drained, before the members go
     if (device >= 0) (void)hipSetDevice(device);
-    if (stream) {
-      (void)hipStreamSynchronize(stream);
-      (void)hipStreamDestroy(stream);
-    }
-    stream = nullptr;
-    for (DevArena *a : {&io, &slabs, &misc, &pinned}) a->release();
-    if (hostIo) (void)hipHostFree(hostIo);
-    hostIo = nullptr;
-    hostIoCap = 0;
-    pinnedHost = nullptr;
-    device = -1;
+    if (stream) (void)hipStreamSynchronize(stream.get());
+    static_cast<L1State &>(*this) = L1State();
   }
   ~L1Ctx() { release(); }
 };
@@ -2995,10 +2856,10 @@ int l1_prepare(L1Ctx &C) {
     C.release();
     C.device = dev;
   }
-  if (!C.stream) HIP_TRY(hipStreamCreateWithFlags(&C.stream, hipStreamNonBlocking));
-  if (!C.misc.p) {
+  if (!C.stream) HIP_TRY(hipStreamCreateWithFlags(C.stream.put(), hipStreamNonBlocking));
+  if (!C.misc.get()) {
     HIP_TRY(C.misc.reserve(kZeroRowBytes));
-    HIP_TRY(hipMemsetAsync(C.misc.p, 0, kZeroRowBytes, C.stream));
+    HIP_TRY(hipMemsetAsync(C.misc.get(), 0, kZeroRowBytes, C.stream.get()));
   }
   return YCNR_OK;
 }
@@ -3011,8 +2872,8 @@ int pin_fixed(const T *fixed, int64_t rows, int k, int dtype) {
   if (rc) return rc;
   const size_t bytes = (size_t)rows * k * sizeof(T);
   HIP_TRY(C.pinned.reserve(bytes));
-  HIP_TRY(hipMemcpyAsync(C.pinned.p, fixed, bytes, hipMemcpyHostToDevice, C.stream));
-  HIP_TRY(hipStreamSynchronize(C.stream));
+  HIP_TRY(hipMemcpyAsync(C.pinned.get(), fixed, bytes, hipMemcpyHostToDevice, C.stream.get()));
+  HIP_TRY(hipStreamSynchronize(C.stream.get()));
   C.pinnedHost = fixed;
   C.pinnedRows = rows;
   C.pinnedK = k;
@@ -3103,9 +2964,9 @@ int64_t als_calc_portion(double lambda, int k, const int32_t *alsRows, const int
   const size_t oFixed = al(oVals + sizeof(T) * (size_t)total + 64);
   const size_t ioBytes = al(oFixed + (pinned ? 0 : sizeof(T) * uniq.size() * (size_t)k));
   L1_TRY(C.io.reserve(ioBytes));
-  L1_TRY(C.reserve_host(ioBytes));
+  L1_TRY(C.hostIo.reserve(ioBytes));
   L1_TRY(C.slabs.reserve(sizeof(T) * std::max<size_t>(1, (size_t)plan.arenaSlabs * slabElems)));
-  char *hb = (char *)C.hostIo, *db = (char *)C.io.p;
+  char *hb = (char *)C.hostIo.get(), *db = (char *)C.io.get();
   memset(hb + oErr, 0, sizeof(ErrInfo));
   if (!units.empty()) memcpy(hb + oUnits, units.data(), sizeof(Unit) * units.size());
   if (!split.empty()) memcpy(hb + oSplit, split.data(), sizeof(SplitRow) * split.size());
@@ -3122,15 +2983,15 @@ int64_t als_calc_portion(double lambda, int k, const int32_t *alsRows, const int
     for (size_t u = 0; u < uniq.size(); ++u) memcpy(cfix + u * k, fixedFactors + (size_t)uniq[u] * k, sizeof(T) * k);
   }
   memcpy(hb + oVals, alsVals, sizeof(T) * (size_t)total);
-  hipStream_t stream = C.stream;
+  hipStream_t stream = C.stream.get();
   ErrInfo *dErr = (ErrInfo *)(db + oErr);
-  T *dZeros = (T *)C.misc.p;
+  T *dZeros = (T *)C.misc.get();
   L1_TRY(hipMemcpyAsync(db + oErr, hb + oErr, ioBytes - oErr, hipMemcpyHostToDevice, stream));
   {
     // rows are numbered 0..nRows-1 on the device and scattered to rowId on the host
-    const T *dFixed = pinned ? (const T *)C.pinned.p : (const T *)(db + oFixed);
+    const T *dFixed = pinned ? (const T *)C.pinned.get() : (const T *)(db + oFixed);
     StepArgs<T> a{(const Unit *)(db + oUnits), (const SplitRow *)(db + oSplit), (const int32_t *)(db + oIndx), (const T *)(db + oVals), dFixed, dZeros,
-                  (T *)(db + oSolved), (T *)C.slabs.p, dErr, lambda, k, 0, 0, 0u};
+                  (T *)(db + oSolved), (T *)C.slabs.get(), dErr, lambda, k, 0, 0, 0u};
     if ((rc = launch_out_of_place<T>(a, plan, stream))) return rc;
   }
   // rows without ratings are never written by the kernels and never copied back below
