@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define YCNR_ALS_ABI_VERSION 4 /* 4: + ycnr_als_comm_info, ycnr_als_last_rmse_ms (nothing changed or removed); later, still 4: + ycnr_als_recommend, + ycnr_als_fold_in, ycnr_als_recommend_for_ratings */
+#define YCNR_ALS_ABI_VERSION 4 /* 4: + ycnr_als_comm_info, ycnr_als_last_rmse_ms (nothing changed or removed); later, still 4: + ycnr_als_recommend, + ycnr_als_fold_in, ycnr_als_recommend_for_ratings; later, still 4: + ycnr_als_step_implicit */
 
 /* error codes */
 #define YCNR_OK 0
@@ -488,6 +488,30 @@ int ycnr_als_recommend_for_ratings(ycnr_als *h, int64_t nUsers, const int64_t *r
                                    const int64_t *skipPtr, const int32_t *skipIds, double globalAvgShift, double minRecommendRating,
                                    int32_t limit, int32_t *outIds, double *outPredict, int32_t *outCount, void *outRows /* may be NULL */,
                                    int32_t *outStatus, double *deviceMs);
+
+/* ---- Implicit feedback: the half-step of Hu, Koren, Volinsky 2008 ---------------------------------
+ *
+ * The reference factorises explicit ratings only and lists titles a user watched but never rated under "you can not"; the
+ * header of lib/emf/Emf.js points at the method for such data ("implicit matrix factorization: yifanhu.net/PUB/cf.pdf").
+ * One half-step of it, for the side's rows u with observations S_u and raw values r_ui (the CSR uploaded with
+ * ycnr_als_set_ratings(side, ...)), Y = ALL rows of the fixed opposite matrix:
+ *     G   = Y^T Y                                         once per half-step
+ *     A_u = G + alpha sum_{i in S_u} r_ui y_i y_i^T + lambda I
+ *     b_u =     sum_{i in S_u} (1 + alpha r_ui) y_i       confidence c = 1 + alpha r, preference 1
+ *     x_u = A_u^-1 b_u, written in place like ycnr_als_step
+ *   lambda    the side's userFactReg / itemFactReg of the handle's options, used PLAIN (the paper's), not times n
+ *   A row of the shard WITHOUT observations has the exact solution x = 0 and is written as zeros -- unlike ycnr_als_step, which
+ *   leaves such rows alone: a never-seen user must not recommend from its random start.  Rows outside the shard are untouched.
+ *   badRows   (may be NULL) rows with a pivot p where !(p > 0): those rows become zeros and the call still returns YCNR_OK.
+ *             Values are not validated; a negative r can make A indefinite and shows up here.
+ *   msOut3    (may be NULL) {gramMs, rowsMs, totalMs}: G and its reduction, the row kernels, both -- from HIP events.
+ * Enqueued on the handle's stream behind anything queued there; returns after the stream has drained.  G is summed in float64
+ * in an order that depends on the fixed side's row count alone; every row is solved in float64 from its own sums (accumulated
+ * in the handle's precision) and rounded once.  ycnr_als_recommend and, for the explicit model, fold-in serve the result unchanged.
+ * YCNR_ERR_INVALID: null handle, bad side, alpha negative or not finite.  YCNR_ERR_STATE: no ratings for the side; half-steps
+ * enqueued with ycnr_als_step_async and not yet completed by ycnr_als_sync.  YCNR_ERR_UNSUPPORTED: factorsCount > 128, a
+ * communicator with world > 1, a banded side, a side uploaded in more than one piece.  The matrices are untouched then. */
+int ycnr_als_step_implicit(ycnr_als *h, int side, double alpha, int32_t *badRows /* may be NULL */, double *msOut3 /* may be NULL */);
 
 #ifdef __cplusplus
 }

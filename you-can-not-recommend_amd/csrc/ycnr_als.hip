@@ -18,6 +18,7 @@
 #include <hipcub/hipcub.hpp>
 #include "recommend_kernels.hip.h"
 #include "foldin_kernels.hip.h"
+#include "implicit_kernels.hip.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -706,9 +707,21 @@ int check_index_bounds(const int32_t *dIndx, int64_t n, int64_t lo, int64_t hi, 
 
 // one pipelined piece of a side's row shard: its ratings, its work-unit schedule and the events
 // that time its kernels and its exchange
+// The plan of the implicit half-step (ycnr_als_step_implicit) for a piece: built by the first such half-step after the upload,
+// kept with the Part and dropped with it by the next upload
+struct ImplicitPlan {
+  bool built = false;
+  int64_t nUnits = 0, nSplit = 0, nSlabs = 0, nEmpty = 0;
+  DevPtr<Unit> dUnits;
+  DevPtr<SplitRow> dSplit;
+  DevPtr<int32_t> dEmpty;  // rows of the piece without observations
+};
+
 struct Part {
   Ratings R;
   Schedule S;
+  std::vector<int64_t> hostPtr;  // the piece's row pointer as uploaded (8 bytes per row): what ImplicitPlan is built from
+  ImplicitPlan implicit;
   Event ev[5], ready, x0, x1;
   // fork / join of the piece's dual-class launches on the handle's side streams, and "all kernels of the piece done":
   // per piece, because two pieces are in flight at a time (on the handle's two piece streams)
@@ -798,6 +811,14 @@ struct ycnr_als {
          FOLD_PTR, FOLD_INDX, FOLD_VALS, FOLD_ROWS, FOLD_STATUS, FOLD_STORE, FOLD_UNITS, FOLD_SPLIT, FOLD_SLABS, FOLD_ERR, FOLD_PAD, REC_NBUF };
   GrowBuf<ExactAlloc> rec[REC_NBUF];
   Event recEv[2];
+  // ycnr_als_step_implicit: G, its per-slice partials and the slabs of split rows (grow-only: a second half-step of the same size
+  // allocates nothing), the bad-row count and the three timing events
+  struct Implicit {
+    GrowBuf<ExactAlloc> gram, partial, slabs;
+    DevPtr<int32_t> dBad;
+    HostPtr<int32_t> hBad;
+    Event ev[3];
+  } implicit;
   PiecePlan foldPlan;  // ycnr_als_fold_in beyond 128 factors: the plan whose lists are being copied to the device
   DevPtr<ErrInfo> dErr;
   // The error record is never reset on the device: its count only grows, the host remembers what it has seen
@@ -1423,6 +1444,8 @@ static int build_part(ycnr_als *h, int side, const int64_t *rowPtr, const int32_
   }
   part.R = std::move(newR);
   part.S = std::move(S);
+  part.hostPtr = std::move(hp);
+  part.implicit = ImplicitPlan();
   return YCNR_OK;
 }
 
@@ -2232,6 +2255,120 @@ int ycnr_als_step(ycnr_als *h, int side) {
   int rc = ycnr_als_step_async(h, side);
   if (rc) return rc;
   return ycnr_als_sync(h);
+}
+
+// ---- implicit-feedback half-step (implicit_kernels.hip.h) ----
+extern "C++" {
+namespace {
+// Units, split rows and empty rows of the piece, from the row pointer kept at upload; `chunk` ratings per unit and per whole row
+int implicit_build_plan(Part &part, int chunk) {
+  ImplicitPlan N;
+  std::vector<Unit> units;
+  std::vector<SplitRow> split;
+  std::vector<int32_t> empty;
+  int64_t solved = 0;
+  const int64_t nRows = part.R.rowEnd - part.R.rowBegin;
+  build_schedule(part.hostPtr.data(), part.R.rowBegin, nRows, chunk, units, split, N.nSlabs, solved, -1, chunk, kMaxSlabsPerRow);
+  for (int64_t r = 0; r < nRows; ++r)
+    if (part.hostPtr[(size_t)r + 1] == part.hostPtr[(size_t)r]) empty.push_back((int32_t)(part.R.rowBegin + r));
+  N.nUnits = (int64_t)units.size(), N.nSplit = (int64_t)split.size(), N.nEmpty = (int64_t)empty.size();
+  if (N.nUnits) {
+    HIP_TRY(hipMalloc(N.dUnits.put(), sizeof(Unit) * units.size()));
+    HIP_TRY(hipMemcpy(N.dUnits.get(), units.data(), sizeof(Unit) * units.size(), hipMemcpyHostToDevice));
+  }
+  if (N.nSplit) {
+    HIP_TRY(hipMalloc(N.dSplit.put(), sizeof(SplitRow) * split.size()));
+    HIP_TRY(hipMemcpy(N.dSplit.get(), split.data(), sizeof(SplitRow) * split.size(), hipMemcpyHostToDevice));
+  }
+  if (N.nEmpty) {
+    HIP_TRY(hipMalloc(N.dEmpty.put(), sizeof(int32_t) * empty.size()));
+    HIP_TRY(hipMemcpy(N.dEmpty.get(), empty.data(), sizeof(int32_t) * empty.size(), hipMemcpyHostToDevice));
+  }
+  N.built = true;
+  part.implicit = std::move(N);
+  return YCNR_OK;
+}
+
+// gram -> gram-reduce -> units -> reduce-solve -> zero rows, all on the handle's stream
+template <typename T>
+int implicit_enqueue(ycnr_als *h, int side, Part &part, double alpha) {
+  ycnr_als::Implicit &I = h->implicit;
+  const ImplicitPlan &P = part.implicit;
+  const int k = h->opt.factorsCount, nb = (k + 15) / 16, kp = nb * 16, nt = tile_count(nb);
+  const int64_t m = h->rows(1 - side), sliceRows = implicit_slice_rows(m), nSlices = (m + sliceRows - 1) / sliceRows;
+  const T *fixed = (const T *)h->factors[1 - side];
+  HIP_TRY(I.gram.reserve((size_t)kp * kp * sizeof(double)));
+  HIP_TRY(I.partial.reserve((size_t)nSlices * nt * 256 * sizeof(double)));
+  if (P.nSlabs) HIP_TRY(I.slabs.reserve((size_t)P.nSlabs * (size_t)implicit_slab_elems(k) * sizeof(double)));
+  if (!I.dBad) HIP_TRY(hipMalloc(I.dBad.put(), sizeof(int32_t)));
+  if (!I.hBad) HIP_TRY(hipHostMalloc((void **)I.hBad.put(), sizeof(int32_t), hipHostMallocDefault));
+  for (Event &e : I.ev)
+    if (!e) HIP_TRY(hipEventCreate(e.put()));
+  double *G = (double *)I.gram.get(), *partial = (double *)I.partial.get();
+  // 16-byte loads: rows of k elements that are whole vectors, from a 16-byte aligned matrix (a bound one may not be)
+  const bool vec = k % (int)(16 / sizeof(T)) == 0 && (reinterpret_cast<uintptr_t>(fixed) & 15) == 0;
+  const size_t gramLds = implicit_gram_lds_bytes(k), unitLds = implicit_unit_lds_bytes(k, sizeof(T)), redLds = implicit_reduce_lds_bytes(k);
+  if (int rc = set_max_lds(reinterpret_cast<const void *>(implicit_unit_kernel<T>), unitLds)) return rc;
+  if (int rc = set_max_lds(reinterpret_cast<const void *>(implicit_reduce_solve_kernel<T>), redLds)) return rc;
+  HIP_TRY(hipEventRecord(I.ev[0].get(), h->stream));
+  if (vec)
+    hipLaunchKernelGGL((implicit_gram_kernel<T, true>), dim3((unsigned)nSlices), dim3(256), gramLds, h->stream, fixed, m, k, sliceRows, partial);
+  else
+    hipLaunchKernelGGL((implicit_gram_kernel<T, false>), dim3((unsigned)nSlices), dim3(256), gramLds, h->stream, fixed, m, k, sliceRows, partial);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(implicit_gram_reduce_kernel, dim3((unsigned)nt), dim3(256), 0, h->stream, (const double *)partial, (int)nSlices, k, G, I.dBad.get());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(I.ev[1].get(), h->stream));
+  const double lambda = side == YCNR_BY_USER ? h->opt.userFactReg : h->opt.itemFactReg;
+  ImplicitArgs<T> a{P.dUnits.get(), P.dSplit.get(), part.R.dIndx.get(), (const T *)part.R.dVals.get(), fixed, (T *)h->factors[side],
+                    G, (double *)I.slabs.get(), I.dBad.get(), alpha, lambda, k};
+  if (P.nUnits) {
+    hipLaunchKernelGGL(implicit_unit_kernel<T>, dim3((unsigned)P.nUnits), dim3(256), unitLds, h->stream, a);
+    HIP_TRY(hipGetLastError());
+  }
+  if (P.nSplit) {
+    hipLaunchKernelGGL(implicit_reduce_solve_kernel<T>, dim3((unsigned)P.nSplit), dim3(256), redLds, h->stream, a);
+    HIP_TRY(hipGetLastError());
+  }
+  if (P.nEmpty) {
+    hipLaunchKernelGGL(implicit_zero_rows_kernel<T>, dim3((unsigned)((P.nEmpty * k + 255) / 256)), dim3(256), 0, h->stream,
+                       (const int32_t *)P.dEmpty.get(), P.nEmpty, k, (T *)h->factors[side]);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipEventRecord(I.ev[2].get(), h->stream));
+  HIP_TRY(hipMemcpyAsync(I.hBad.get(), I.dBad.get(), sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  return YCNR_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int ycnr_als_step_implicit(ycnr_als *h, int side, double alpha, int32_t *badRows, double *msOut3) {
+  if (!h) return fail(YCNR_ERR_INVALID, "null handle");
+  if (side != YCNR_BY_USER && side != YCNR_BY_ITEM) return fail(YCNR_ERR_INVALID, "bad side %d", side);
+  if (!(alpha >= 0.0) || !std::isfinite(alpha)) return fail(YCNR_ERR_INVALID, "ycnr_als_step_implicit: alpha must be finite and >= 0");
+  if (h->opt.factorsCount > kImplicitMaxK)
+    return fail(YCNR_ERR_UNSUPPORTED, "ycnr_als_step_implicit: factorsCount %d > %d", h->opt.factorsCount, kImplicitMaxK);
+  std::vector<Part> &parts = h->parts[side];
+  if (parts.empty()) return fail(YCNR_ERR_STATE, "ycnr_als_step_implicit: set_ratings was not called for this side");
+  if (h->infoPending) return fail(YCNR_ERR_STATE, "ycnr_als_step_implicit: half-steps are in flight (ycnr_als_sync first)");
+  if (h->comm.active() && h->comm.world > 1) return fail(YCNR_ERR_UNSUPPORTED, "ycnr_als_step_implicit: not with a communicator of several ranks");
+  if (h->banded[side].on) return fail(YCNR_ERR_UNSUPPORTED, "ycnr_als_step_implicit: not for a banded side");
+  if (parts.size() != 1) return fail(YCNR_ERR_UNSUPPORTED, "ycnr_als_step_implicit: the side was uploaded in %zu pieces", parts.size());
+  HIP_TRY(hipSetDevice(h->opt.device));
+  Part &part = parts[0];
+  if (!part.implicit.built)
+    if (int rc = implicit_build_plan(part, h->autoChunk ? kImplicitChunk : h->opt.chunkRatings)) return rc;
+  if (int rc = h->opt.dtype == YCNR_F64 ? implicit_enqueue<double>(h, side, part, alpha) : implicit_enqueue<float>(h, side, part, alpha)) return rc;
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (badRows) *badRows = *h->implicit.hBad.get();
+  if (msOut3) {
+    float g = 0, r = 0, t = 0;
+    HIP_TRY(hipEventElapsedTime(&g, h->implicit.ev[0].get(), h->implicit.ev[1].get()));
+    HIP_TRY(hipEventElapsedTime(&r, h->implicit.ev[1].get(), h->implicit.ev[2].get()));
+    HIP_TRY(hipEventElapsedTime(&t, h->implicit.ev[0].get(), h->implicit.ev[2].get()));
+    msOut3[0] = g, msOut3[1] = r, msOut3[2] = t;
+  }
+  return YCNR_OK;
 }
 
 int ycnr_als_last_step_info(ycnr_als *h, ycnr_als_step_info *info) {

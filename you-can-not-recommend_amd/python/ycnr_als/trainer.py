@@ -324,6 +324,15 @@ class AlsDevice:
         check(self._L.ycnr_als_step(self._h, SIDES[side]))
         return self.last_step_info()
 
+    def step_implicit(self, side, alpha):
+        """One implicit-feedback half-step (Hu, Koren, Volinsky 2008; ycnr_als_step_implicit) of `side` from the ratings uploaded
+        with set_ratings: confidence 1 + alpha r, the side's regularisation used plain; rows without observations become zeros.
+        Returns (badRows, ms) with ms = np.array([gramMs, rowsMs, totalMs])."""
+        bad = C.c_int32(0)
+        ms = np.zeros(3, np.float64)
+        check(self._L.ycnr_als_step_implicit(self._h, SIDES[side], float(alpha), C.byref(bad), ms.ctypes.data))
+        return bad.value, ms
+
     def step_async(self, side):
         check(self._L.ycnr_als_step_async(self._h, SIDES[side]))
 
