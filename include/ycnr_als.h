@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define YCNR_ALS_ABI_VERSION 4 /* 4: + ycnr_als_comm_info, ycnr_als_last_rmse_ms (nothing changed or removed); later, still 4: + ycnr_als_recommend, + ycnr_als_fold_in, ycnr_als_recommend_for_ratings; later, still 4: + ycnr_als_step_implicit */
+#define YCNR_ALS_ABI_VERSION 4 /* 4: + ycnr_als_comm_info, ycnr_als_last_rmse_ms (nothing changed or removed); later, still 4: + ycnr_als_recommend, + ycnr_als_fold_in, ycnr_als_recommend_for_ratings; later, still 4: + ycnr_als_step_implicit; later, still 4: + ycnr_als_step_implicit_cg */
 
 /* error codes */
 #define YCNR_OK 0
@@ -512,6 +512,30 @@ int ycnr_als_recommend_for_ratings(ycnr_als *h, int64_t nUsers, const int64_t *r
  * enqueued with ycnr_als_step_async and not yet completed by ycnr_als_sync.  YCNR_ERR_UNSUPPORTED: factorsCount > 128, a
  * communicator with world > 1, a banded side, a side uploaded in more than one piece.  The matrices are untouched then. */
 int ycnr_als_step_implicit(ycnr_als *h, int side, double alpha, int32_t *badRows /* may be NULL */, double *msOut3 /* may be NULL */);
+
+/* The same half-step by a fixed, small number of conjugate-gradient steps per row, warm-started from the row as it stands in
+ * the handle (Takacs, Pilaszy, Tikk 2011): the usual cheap trainer for implicit feedback.  With G, lambda, S_u, r_i as above,
+ * w_i = alpha r_i, c_i = 1 + w_i, for every row u of the shard that the plan keeps whole:
+ *     op(v) = G v + lambda v + sum_{i in S_u} w_i (y_i . v) y_i
+ *     x = the row as it stands;   r = sum_i c_i y_i - op(x);   p = r;   rho = r . r
+ *     repeat cgSteps times, unless the row has stopped:
+ *         q = op(p);  d = p . q
+ *         if rho == 0 or !(d > 0): the row stops (x stays as it is)
+ *         a = rho / d;  x += a p;  r -= a q;  rho' = r . r;  p = r + (rho' / rho) p;  rho = rho'
+ *     store x, rounded once to the handle's type
+ * x, r, p, q, every dot product and the scalars are float64 for both handle precisions; every sum's order depends on the row
+ * alone, so the same request gives the same bits.  Per step a row of n observations costs 2 n k multiply-adds and a share of
+ * one product with G, against the n k^2 Gramian and k^3 / 3 factorisation of the exact solve.
+ *   Rows without observations become zeros and rows outside the shard are untouched, as above.  Rows longer than a work unit's
+ *   chunk (options.chunkRatings, else the library's 4096) are few and bound by their Gramian: they are solved exactly, by the
+ *   kernels of ycnr_als_step_implicit.
+ *   cgSteps   1 .. 64
+ *   badRows   (may be NULL) rows whose stored result would not be finite (they become zeros), plus the exactly solved rows
+ *             counted as above.
+ *   msOut3    as above; rowsMs covers the conjugate-gradient kernel and the exact kernels of the long rows.
+ * Refusals as ycnr_als_step_implicit, and YCNR_ERR_INVALID for cgSteps < 1 or > 64.  The matrices are untouched then. */
+int ycnr_als_step_implicit_cg(ycnr_als *h, int side, double alpha, int32_t cgSteps, int32_t *badRows /* may be NULL */,
+                              double *msOut3 /* may be NULL */);
 
 #ifdef __cplusplus
 }

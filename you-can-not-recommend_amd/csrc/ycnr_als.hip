@@ -19,6 +19,7 @@
 #include "recommend_kernels.hip.h"
 #include "foldin_kernels.hip.h"
 #include "implicit_kernels.hip.h"
+#include "implicit_cg_kernels.hip.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -2339,8 +2340,110 @@ int implicit_enqueue(ycnr_als *h, int side, Part &part, double alpha) {
   HIP_TRY(hipMemcpyAsync(I.hBad.get(), I.dBad.get(), sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
   return YCNR_OK;
 }
+
+// gram -> gram-reduce -> 16 whole rows per workgroup by conjugate gradients -> the chunks of split rows -> their exact
+// reduce-solve -> zero rows.  build_schedule leaves the plan's units as [chunks (nSlabs of them) | whole rows, longest first,
+// ties in row order]: the head of the list is the launch of implicit_unit_kernel over chunks alone, the tail is the batch list
+// (a batch's unused places are those past nRows).
+template <typename T>
+int implicit_cg_enqueue(ycnr_als *h, int side, Part &part, double alpha, int cgSteps) {
+  ycnr_als::Implicit &I = h->implicit;
+  const ImplicitPlan &P = part.implicit;
+  const int k = h->opt.factorsCount, nb = (k + 15) / 16, kp = nb * 16, nt = tile_count(nb);
+  const int64_t m = h->rows(1 - side), sliceRows = implicit_slice_rows(m), nSlices = (m + sliceRows - 1) / sliceRows;
+  const int64_t nChunks = P.nSlabs, nWhole = P.nUnits - P.nSlabs, nBatches = (nWhole + kImplicitCgBatch - 1) / kImplicitCgBatch;
+  const T *fixed = (const T *)h->factors[1 - side];
+  HIP_TRY(I.gram.reserve((size_t)kp * kp * sizeof(double)));
+  HIP_TRY(I.partial.reserve((size_t)nSlices * nt * 256 * sizeof(double)));
+  if (P.nSlabs) HIP_TRY(I.slabs.reserve((size_t)P.nSlabs * (size_t)implicit_slab_elems(k) * sizeof(double)));
+  if (!I.dBad) HIP_TRY(hipMalloc(I.dBad.put(), sizeof(int32_t)));
+  if (!I.hBad) HIP_TRY(hipHostMalloc((void **)I.hBad.put(), sizeof(int32_t), hipHostMallocDefault));
+  for (Event &e : I.ev)
+    if (!e) HIP_TRY(hipEventCreate(e.put()));
+  double *G = (double *)I.gram.get(), *partial = (double *)I.partial.get();
+  const bool vec = k % (int)(16 / sizeof(T)) == 0 && (reinterpret_cast<uintptr_t>(fixed) & 15) == 0;
+  const size_t gramLds = implicit_gram_lds_bytes(k), unitLds = implicit_unit_lds_bytes(k, sizeof(T)), redLds = implicit_reduce_lds_bytes(k),
+               cgLds = implicit_cg_lds_bytes(k);
+  static constexpr void (*kCg[8])(ImplicitCgArgs<T>) = {implicit_cg_kernel<T, 1>, implicit_cg_kernel<T, 2>, implicit_cg_kernel<T, 3>,
+                                                        implicit_cg_kernel<T, 4>, implicit_cg_kernel<T, 5>, implicit_cg_kernel<T, 6>,
+                                                        implicit_cg_kernel<T, 7>, implicit_cg_kernel<T, 8>};  // by 16-column blocks
+  if (int rc = set_max_lds(reinterpret_cast<const void *>(kCg[nb - 1]), cgLds)) return rc;
+  if (int rc = set_max_lds(reinterpret_cast<const void *>(implicit_unit_kernel<T>), unitLds)) return rc;
+  if (int rc = set_max_lds(reinterpret_cast<const void *>(implicit_reduce_solve_kernel<T>), redLds)) return rc;
+  HIP_TRY(hipEventRecord(I.ev[0].get(), h->stream));
+  if (vec)
+    hipLaunchKernelGGL((implicit_gram_kernel<T, true>), dim3((unsigned)nSlices), dim3(256), gramLds, h->stream, fixed, m, k, sliceRows, partial);
+  else
+    hipLaunchKernelGGL((implicit_gram_kernel<T, false>), dim3((unsigned)nSlices), dim3(256), gramLds, h->stream, fixed, m, k, sliceRows, partial);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(implicit_gram_reduce_kernel, dim3((unsigned)nt), dim3(256), 0, h->stream, (const double *)partial, (int)nSlices, k, G, I.dBad.get());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(I.ev[1].get(), h->stream));
+  const double lambda = side == YCNR_BY_USER ? h->opt.userFactReg : h->opt.itemFactReg;
+  if (nBatches) {
+    ImplicitCgArgs<T> c{P.dUnits.get() + nChunks, nWhole, part.R.dIndx.get(), (const T *)part.R.dVals.get(), fixed, (T *)h->factors[side],
+                        G, I.dBad.get(), alpha, lambda, k, cgSteps};
+    hipLaunchKernelGGL(kCg[nb - 1], dim3((unsigned)nBatches), dim3(256), cgLds, h->stream, c);
+    HIP_TRY(hipGetLastError());
+  }
+  ImplicitArgs<T> a{P.dUnits.get(), P.dSplit.get(), part.R.dIndx.get(), (const T *)part.R.dVals.get(), fixed, (T *)h->factors[side],
+                    G, (double *)I.slabs.get(), I.dBad.get(), alpha, lambda, k};
+  if (nChunks) {
+    hipLaunchKernelGGL(implicit_unit_kernel<T>, dim3((unsigned)nChunks), dim3(256), unitLds, h->stream, a);
+    HIP_TRY(hipGetLastError());
+  }
+  if (P.nSplit) {
+    hipLaunchKernelGGL(implicit_reduce_solve_kernel<T>, dim3((unsigned)P.nSplit), dim3(256), redLds, h->stream, a);
+    HIP_TRY(hipGetLastError());
+  }
+  if (P.nEmpty) {
+    hipLaunchKernelGGL(implicit_zero_rows_kernel<T>, dim3((unsigned)((P.nEmpty * k + 255) / 256)), dim3(256), 0, h->stream,
+                       (const int32_t *)P.dEmpty.get(), P.nEmpty, k, (T *)h->factors[side]);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipEventRecord(I.ev[2].get(), h->stream));
+  HIP_TRY(hipMemcpyAsync(I.hBad.get(), I.dBad.get(), sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  return YCNR_OK;
+}
+
+// the refusals of ycnr_als_step_implicit, then the plan of the side's piece if it is not built yet; `who`: for the message
+int implicit_cg_prepare(ycnr_als *h, int side, double alpha, const char *who) {
+  if (!h) return fail(YCNR_ERR_INVALID, "null handle");
+  if (side != YCNR_BY_USER && side != YCNR_BY_ITEM) return fail(YCNR_ERR_INVALID, "bad side %d", side);
+  if (!(alpha >= 0.0) || !std::isfinite(alpha)) return fail(YCNR_ERR_INVALID, "%s: alpha must be finite and >= 0", who);
+  if (h->opt.factorsCount > kImplicitMaxK) return fail(YCNR_ERR_UNSUPPORTED, "%s: factorsCount %d > %d", who, h->opt.factorsCount, kImplicitMaxK);
+  std::vector<Part> &parts = h->parts[side];
+  if (parts.empty()) return fail(YCNR_ERR_STATE, "%s: set_ratings was not called for this side", who);
+  if (h->infoPending) return fail(YCNR_ERR_STATE, "%s: half-steps are in flight (ycnr_als_sync first)", who);
+  if (h->comm.active() && h->comm.world > 1) return fail(YCNR_ERR_UNSUPPORTED, "%s: not with a communicator of several ranks", who);
+  if (h->banded[side].on) return fail(YCNR_ERR_UNSUPPORTED, "%s: not for a banded side", who);
+  if (parts.size() != 1) return fail(YCNR_ERR_UNSUPPORTED, "%s: the side was uploaded in %zu pieces", who, parts.size());
+  HIP_TRY(hipSetDevice(h->opt.device));
+  if (!parts[0].implicit.built) return implicit_build_plan(parts[0], h->autoChunk ? kImplicitChunk : h->opt.chunkRatings);
+  return YCNR_OK;
+}
 }  // namespace
 }  // extern "C++"
+
+int ycnr_als_step_implicit_cg(ycnr_als *h, int side, double alpha, int32_t cgSteps, int32_t *badRows, double *msOut3) {
+  if (cgSteps < 1 || cgSteps > kImplicitCgMaxSteps)
+    return fail(YCNR_ERR_INVALID, "ycnr_als_step_implicit_cg: cgSteps %d outside 1 .. %d", cgSteps, kImplicitCgMaxSteps);
+  if (int rc = implicit_cg_prepare(h, side, alpha, "ycnr_als_step_implicit_cg")) return rc;
+  Part &part = h->parts[side][0];
+  if (int rc = h->opt.dtype == YCNR_F64 ? implicit_cg_enqueue<double>(h, side, part, alpha, cgSteps)
+                                        : implicit_cg_enqueue<float>(h, side, part, alpha, cgSteps))
+    return rc;
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (badRows) *badRows = *h->implicit.hBad.get();
+  if (msOut3) {
+    float g = 0, r = 0, t = 0;
+    HIP_TRY(hipEventElapsedTime(&g, h->implicit.ev[0].get(), h->implicit.ev[1].get()));
+    HIP_TRY(hipEventElapsedTime(&r, h->implicit.ev[1].get(), h->implicit.ev[2].get()));
+    HIP_TRY(hipEventElapsedTime(&t, h->implicit.ev[0].get(), h->implicit.ev[2].get()));
+    msOut3[0] = g, msOut3[1] = r, msOut3[2] = t;
+  }
+  return YCNR_OK;
+}
 
 int ycnr_als_step_implicit(ycnr_als *h, int side, double alpha, int32_t *badRows, double *msOut3) {
   if (!h) return fail(YCNR_ERR_INVALID, "null handle");

@@ -324,13 +324,18 @@ class AlsDevice:
         check(self._L.ycnr_als_step(self._h, SIDES[side]))
         return self.last_step_info()
 
-    def step_implicit(self, side, alpha):
+    def step_implicit(self, side, alpha, cg_steps=None):
         """One implicit-feedback half-step (Hu, Koren, Volinsky 2008; ycnr_als_step_implicit) of `side` from the ratings uploaded
         with set_ratings: confidence 1 + alpha r, the side's regularisation used plain; rows without observations become zeros.
+        cg_steps: None solves every row exactly; an integer 1 .. 64 runs that many conjugate-gradient steps per row from the
+        row as it stands (ycnr_als_step_implicit_cg; rows longer than a work unit's chunk are still solved exactly).
         Returns (badRows, ms) with ms = np.array([gramMs, rowsMs, totalMs])."""
         bad = C.c_int32(0)
         ms = np.zeros(3, np.float64)
-        check(self._L.ycnr_als_step_implicit(self._h, SIDES[side], float(alpha), C.byref(bad), ms.ctypes.data))
+        if cg_steps is None:
+            check(self._L.ycnr_als_step_implicit(self._h, SIDES[side], float(alpha), C.byref(bad), ms.ctypes.data))
+        else:
+            check(self._L.ycnr_als_step_implicit_cg(self._h, SIDES[side], float(alpha), int(cg_steps), C.byref(bad), ms.ctypes.data))
         return bad.value, ms
 
     def step_async(self, side):
