@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define YCNR_ALS_ABI_VERSION 4 /* 4: + ycnr_als_comm_info, ycnr_als_last_rmse_ms (nothing changed or removed); later, still 4: + ycnr_als_recommend, + ycnr_als_fold_in, ycnr_als_recommend_for_ratings; later, still 4: + ycnr_als_step_implicit; later, still 4: + ycnr_als_step_implicit_cg */
+#define YCNR_ALS_ABI_VERSION 4 /* 4: + ycnr_als_comm_info, ycnr_als_last_rmse_ms (nothing changed or removed); later, still 4: + ycnr_als_recommend, + ycnr_als_fold_in, ycnr_als_recommend_for_ratings; later, still 4: + ycnr_als_step_implicit; later, still 4: + ycnr_als_step_implicit_cg; later, still 4: + ycnr_als_rank_eval */
 
 /* error codes */
 #define YCNR_OK 0
@@ -536,6 +536,40 @@ int ycnr_als_step_implicit(ycnr_als *h, int side, double alpha, int32_t *badRows
  * Refusals as ycnr_als_step_implicit, and YCNR_ERR_INVALID for cgSteps < 1 or > 64.  The matrices are untouched then. */
 int ycnr_als_step_implicit_cg(ycnr_als *h, int side, double alpha, int32_t cgSteps, int32_t *badRows /* may be NULL */,
                               double *msOut3 /* may be NULL */);
+
+/* ---- Ranking evaluation: where the model places held-out items -------------------------------------
+ *
+ * For the implicit model an RMSE says nothing (every observed preference is 1); Hu, Koren and Volinsky evaluate by the expected
+ * percentile rank of held-out observations in each user's ranking of the whole catalogue, and hit rate at N, MRR and AUC need
+ * the same integer per held-out pair (u, i): how many competing items the model places ahead of i for u.  This entry computes it
+ * on the device from the matrices the handle holds, without a score matrix and without sorting the catalogue
+ * (csrc/rank_kernels.hip.h: scores and counting in one kernel).
+ *   userIds, skipPtr, skipIds   exactly as for ycnr_als_recommend: row ids of the user matrix in any order, repeats allowed;
+ *              offsets relative to the request; skip ids strictly ascending per user, ids outside the catalogue match nothing.
+ *              The skip list is the user's training items.
+ *   testPtr    nUsers + 1 offsets relative to the request (testPtr[0] == 0); testIds: the held-out items of each request user,
+ *              strictly ascending per user, inside [0, totalItemsCount).  At most 2^31 - 1 pairs per call.
+ *   outRank    one per held-out pair q = (u, i), in the order of testIds: the number of COMPETING items j != i that beat i.  An item
+ *              competes for u if its id is in the catalogue and not in u's skip list (the user's other held-out items compete
+ *              like any item); j beats i if s_uj > s_ui, or s_uj == s_ui and j < i -- the total order of ycnr_als_recommend.
+ *              If i itself is in u's skip list, outRank[q] = -1.
+ *   outCandidates   one per request user: the competing items, totalItemsCount minus u's skip ids inside the catalogue.
+ * s is the score of the recommend kernels with the same bits (the same MFMA operand assignment and order, shift 0), so for a
+ * catalogue of at most 4094 items outRank[q] is the position of i in the list ycnr_als_recommend returns for u with limit = 4096
+ * and no threshold.  (YCNR_RECOMMEND_VALU changes the bits of that entry, not of this one.)  A NaN score compares as IEEE
+ * compares it -- it beats nothing and nothing beats it -- and is not otherwise handled: ranks of a matrix with NaNs mean nothing.
+ * Ranks are integers summed with integer atomics: the same request gives the same numbers whatever the grid.
+ * YCNR_ERR_INVALID (outputs untouched): null pointers (testIds / skipIds may be NULL where their lists are all empty), a user id
+ * outside [0, totalUsersCount), testPtr / skipPtr not starting at 0 or decreasing, test or skip ids not strictly ascending, a
+ * test id outside the catalogue.  nUsers == 0 is YCNR_OK; a request without held-out pairs is YCNR_OK and still fills
+ * outCandidates.  YCNR_ERR_UNSUPPORTED: 16 user rows padded to a multiple of 16 factors plus the slot tables (20.1 KB float32,
+ * 28.1 KB float64) and 384 bytes of slot descriptors exceed the kernel's 64 KB of LDS: factorsCount > 688 (float32) or > 272 (float64).
+ * Enqueued on the handle's stream behind the half-steps in flight (like ycnr_als_recommend), returns with the results on the
+ * host; the device buffers stay with the handle (a second call of the same size allocates nothing).  LOCAL, not collective.
+ * deviceMs (may be NULL): the kernels, between two HIP events on the handle's stream. */
+int ycnr_als_rank_eval(ycnr_als *h, int64_t nUsers, const int32_t *userIds, const int64_t *testPtr, const int32_t *testIds,
+                       const int64_t *skipPtr, const int32_t *skipIds, int32_t *outRank, int32_t *outCandidates,
+                       double *deviceMs /* may be NULL */);
 
 #ifdef __cplusplus
 }

@@ -17,6 +17,7 @@
 #include "prep_kernels.hip.h"
 #include <hipcub/hipcub.hpp>
 #include "recommend_kernels.hip.h"
+#include "rank_kernels.hip.h"
 #include "foldin_kernels.hip.h"
 #include "implicit_kernels.hip.h"
 #include "implicit_cg_kernels.hip.h"
@@ -809,7 +810,9 @@ struct ycnr_als {
   enum { REC_USER_IDS, REC_SKIP_PTR, REC_SKIP, REC_PART_V, REC_PART_I, REC_IDS, REC_PRED, REC_CNT, REC_ROWS, REC_SCORES,
          // ycnr_als_fold_in / ycnr_als_recommend_for_ratings: the request's CSR, the solved rows and their status, the ids to store at;
          // factorsCount > 128: the plan of the step kernels (units, split rows, slabs) and their error record
-         FOLD_PTR, FOLD_INDX, FOLD_VALS, FOLD_ROWS, FOLD_STATUS, FOLD_STORE, FOLD_UNITS, FOLD_SPLIT, FOLD_SLABS, FOLD_ERR, FOLD_PAD, REC_NBUF };
+         FOLD_PTR, FOLD_INDX, FOLD_VALS, FOLD_ROWS, FOLD_STATUS, FOLD_STORE, FOLD_UNITS, FOLD_SPLIT, FOLD_SLABS, FOLD_ERR, FOLD_PAD,
+         // ycnr_als_rank_eval: the slots, the held-out ids, a batch's histogram image, target order and skip marks, the two outputs
+         RANK_SLOTS, RANK_TEST, RANK_HIST, RANK_ORDER, RANK_MARK, RANK_OUT, RANK_CAND, REC_NBUF };
   GrowBuf<ExactAlloc> rec[REC_NBUF];
   Event recEv[2];
   // ycnr_als_step_implicit: G, its per-slice partials and the slabs of split rows (grow-only: a second half-step of the same size
@@ -2910,6 +2913,114 @@ int ycnr_als_recommend_for_ratings(ycnr_als *h, int64_t nUsers, const int64_t *r
   };
   return recommend_run(h, h->rec[A::FOLD_ROWS].get(), nUsers, nullptr, skipPtr, skipIds, globalAvgShift, minRecommendRating, limit, outIds, outPredict,
                        outCount, deviceMs, true, (const int32_t *)h->rec[A::FOLD_STATUS].get(), copies);
+}
+
+// ---- ranks of held-out items from the handle's own matrices (rank_kernels.hip.h, rank_plan.h) ----
+extern "C++" {
+namespace {
+// one batch of slots: clear its histogram image and marks, count, turn the histograms into ranks
+template <typename T>
+void launch_rank_batch(ycnr_als *h, int64_t s0, int64_t nb, int64_t nTest) {
+  typedef ycnr_als A;
+  const int k = h->opt.factorsCount;
+  const int64_t totalItems = h->opt.totalItemsCount;
+  const RankSlot *slots = (const RankSlot *)h->rec[A::RANK_SLOTS].get() + s0;
+  int32_t *hist = (int32_t *)h->rec[A::RANK_HIST].get(), *order = (int32_t *)h->rec[A::RANK_ORDER].get(), *mark = (int32_t *)h->rec[A::RANK_MARK].get();
+  const unsigned xblk = (unsigned)((nb + kRankSlotsPerGroup - 1) / kRankSlotsPerGroup), yblk = (unsigned)rank_parts(nb, totalItems, device_cus());
+  hipLaunchKernelGGL(rank_clear_kernel, dim3((unsigned)((nb * kRankBins + 255) / 256)), dim3(256), 0, h->stream, hist, order, mark, nb);
+  hipLaunchKernelGGL(rank_count_kernel<T>, dim3(xblk, yblk), dim3(256), rank_lds_bytes(k, sizeof(T)), h->stream, (const T *)h->factors[YCNR_BY_USER],
+                     (const int32_t *)h->rec[A::REC_USER_IDS].get(), slots, nb, (const int32_t *)h->rec[A::RANK_TEST].get(),
+                     (const T *)h->factors[YCNR_BY_ITEM], totalItems, k, (const int64_t *)h->rec[A::REC_SKIP_PTR].get(),
+                     (const int32_t *)h->rec[A::REC_SKIP].get(), hist, order, mark);
+  hipLaunchKernelGGL(rank_finish_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, h->stream, slots, nb, (const int32_t *)hist, (const int32_t *)order,
+                     (const int32_t *)mark, (int32_t *)h->rec[A::RANK_OUT].get(), nTest);
+}
+}  // namespace
+}  // extern "C++"
+
+int ycnr_als_rank_eval(ycnr_als *h, int64_t nUsers, const int32_t *userIds, const int64_t *testPtr, const int32_t *testIds, const int64_t *skipPtr,
+                       const int32_t *skipIds, int32_t *outRank, int32_t *outCandidates, double *deviceMs) {
+  if (!h) return fail(YCNR_ERR_INVALID, "null handle");
+  if (nUsers < 0 || nUsers > 0x7fffffffLL) return fail(YCNR_ERR_INVALID, "ycnr_als_rank_eval: bad nUsers");
+  if (nUsers == 0) {
+    if (deviceMs) *deviceMs = 0.0;
+    return YCNR_OK;
+  }
+  if (!userIds || !testPtr || !skipPtr || !outRank || !outCandidates) return fail(YCNR_ERR_INVALID, "ycnr_als_rank_eval: null argument");
+  const int k = h->opt.factorsCount;
+  const int64_t totalItems = h->opt.totalItemsCount;
+  if (!rank_supported(k, h->ts()))
+    return fail(YCNR_ERR_UNSUPPORTED, "ycnr_als_rank_eval: 16 user rows of %d factors and the slot tables need %zu bytes of LDS, more than %zu", k,
+                rank_lds_bytes(k, h->ts()) + kRankStaticLds, kRankLdsBudget);
+  for (int64_t u = 0; u < nUsers; ++u)
+    if (userIds[u] < 0 || userIds[u] >= h->opt.totalUsersCount)
+      return fail(YCNR_ERR_INVALID, "ycnr_als_rank_eval: user id %d at position %lld is outside [0, %lld)", userIds[u], (long long)u,
+                  (long long)h->opt.totalUsersCount);
+  if (testPtr[0] != 0) return fail(YCNR_ERR_INVALID, "ycnr_als_rank_eval: testPtr[0] != 0");
+  for (int64_t u = 0; u < nUsers; ++u) {
+    if (testPtr[u + 1] < testPtr[u]) return fail(YCNR_ERR_INVALID, "ycnr_als_rank_eval: testPtr decreases at user %lld", (long long)u);
+    if (testPtr[u + 1] > testPtr[u] && !testIds) return fail(YCNR_ERR_INVALID, "ycnr_als_rank_eval: null testIds");
+    for (int64_t q = testPtr[u]; q < testPtr[u + 1]; ++q) {
+      if (testIds[q] < 0 || testIds[q] >= totalItems)
+        return fail(YCNR_ERR_INVALID, "ycnr_als_rank_eval: test id %d of user %lld is outside [0, %lld)", testIds[q], (long long)u, (long long)totalItems);
+      if (q > testPtr[u] && testIds[q] <= testIds[q - 1])
+        return fail(YCNR_ERR_INVALID, "ycnr_als_rank_eval: test ids of user %lld are not strictly ascending", (long long)u);
+    }
+  }
+  const int64_t nTest = testPtr[nUsers];
+  if (nTest > 0x7fffffffLL) return fail(YCNR_ERR_INVALID, "ycnr_als_rank_eval: more than 2^31 - 1 held-out pairs in one call");
+  if (int rc = check_skip_lists("ycnr_als_rank_eval", nUsers, skipPtr, skipIds)) return rc;
+  const int64_t nSkip = skipPtr[nUsers];
+  const std::vector<RankSlot> slots = rank_cut_slots(nUsers, testPtr);
+  const int64_t nSlots = (int64_t)slots.size(), batch = std::min<int64_t>(nSlots, kRankBatchSlots);
+
+  typedef ycnr_als A;
+  HIP_TRY(hipSetDevice(h->opt.device));
+  for (Event &ev : h->recEv)
+    if (!ev) HIP_TRY(hipEventCreate(ev.put()));
+  HIP_TRY(h->rec[A::REC_USER_IDS].reserve((size_t)nUsers * 4));
+  HIP_TRY(h->rec[A::REC_SKIP_PTR].reserve((size_t)(nUsers + 1) * 8));
+  HIP_TRY(h->rec[A::REC_SKIP].reserve(std::max<size_t>((size_t)nSkip * 4, 8)));
+  HIP_TRY(h->rec[A::RANK_SLOTS].reserve(std::max<size_t>((size_t)nSlots * sizeof(RankSlot), 8)));
+  HIP_TRY(h->rec[A::RANK_TEST].reserve(std::max<size_t>((size_t)nTest * 4, 8)));
+  HIP_TRY(h->rec[A::RANK_HIST].reserve(std::max<size_t>((size_t)batch * kRankBins * 4, 8)));
+  HIP_TRY(h->rec[A::RANK_ORDER].reserve(std::max<size_t>((size_t)batch * kRankSlotTargets * 4, 8)));
+  HIP_TRY(h->rec[A::RANK_MARK].reserve(std::max<size_t>((size_t)batch * kRankSlotTargets * 4, 8)));
+  HIP_TRY(h->rec[A::RANK_OUT].reserve(std::max<size_t>((size_t)nTest * 4, 8)));
+  HIP_TRY(h->rec[A::RANK_CAND].reserve((size_t)nUsers * 4));
+  if (nSlots > 0) {
+    const void *fn = h->opt.dtype == YCNR_F32 ? reinterpret_cast<const void *>(rank_count_kernel<float>) : reinterpret_cast<const void *>(rank_count_kernel<double>);
+    if (int rc = set_max_lds(fn, rank_lds_bytes(k, h->ts()))) return rc;
+  }
+  // everything below is enqueued on the handle's stream: behind the half-steps in flight, like ycnr_als_recommend
+  HIP_TRY(hipMemcpyAsync(h->rec[A::REC_USER_IDS].get(), userIds, (size_t)nUsers * 4, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(h->rec[A::REC_SKIP_PTR].get(), skipPtr, (size_t)(nUsers + 1) * 8, hipMemcpyHostToDevice, h->stream));
+  if (nSkip) HIP_TRY(hipMemcpyAsync(h->rec[A::REC_SKIP].get(), skipIds, (size_t)nSkip * 4, hipMemcpyHostToDevice, h->stream));
+  if (nSlots) {
+    HIP_TRY(hipMemcpyAsync(h->rec[A::RANK_SLOTS].get(), slots.data(), (size_t)nSlots * sizeof(RankSlot), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->rec[A::RANK_TEST].get(), testIds, (size_t)nTest * 4, hipMemcpyHostToDevice, h->stream));
+  }
+  HIP_TRY(hipEventRecord(h->recEv[0].get(), h->stream));
+  for (int64_t s0 = 0; s0 < nSlots; s0 += batch) {
+    const int64_t nb = std::min(batch, nSlots - s0);
+    if (h->opt.dtype == YCNR_F32) launch_rank_batch<float>(h, s0, nb, nTest);
+    else launch_rank_batch<double>(h, s0, nb, nTest);
+    hipError_t le = hipGetLastError();
+    if (le != hipSuccess) return fail(YCNR_ERR_HIP, "rank_eval launch: %s", hipGetErrorString(le));
+  }
+  hipLaunchKernelGGL(rank_candidates_kernel, dim3((unsigned)((nUsers + 255) / 256)), dim3(256), 0, h->stream, (const int64_t *)h->rec[A::REC_SKIP_PTR].get(),
+                     (const int32_t *)h->rec[A::REC_SKIP].get(), nUsers, totalItems, (int32_t *)h->rec[A::RANK_CAND].get());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(h->recEv[1].get(), h->stream));
+  if (nTest) HIP_TRY(hipMemcpyAsync(outRank, h->rec[A::RANK_OUT].get(), (size_t)nTest * 4, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(outCandidates, h->rec[A::RANK_CAND].get(), (size_t)nUsers * 4, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (deviceMs) {
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, h->recEv[0].get(), h->recEv[1].get()));
+    *deviceMs = ms;
+  }
+  return YCNR_OK;
 }
 
 // ---- multi-GPU exchange (comm_impl.hip.h) ----

@@ -8,5 +8,6 @@ from . import _lib
 from ._lib import YcnrError
 from .trainer import (AlsDevice, als_calc_portion, pin_fixed_factors, unpin_fixed_factors, release_portion_state, rmse_portion, split_to_sets,
                       rating_stats, recommend_items)
+from .metrics import ranking_metrics
 
-__all__ = ["AlsDevice", "als_calc_portion", "pin_fixed_factors", "unpin_fixed_factors", "release_portion_state", "rmse_portion", "split_to_sets", "rating_stats", "recommend_items", "YcnrError", "_lib"]
+__all__ = ["AlsDevice", "als_calc_portion", "pin_fixed_factors", "unpin_fixed_factors", "release_portion_state", "rmse_portion", "split_to_sets", "rating_stats", "recommend_items", "ranking_metrics", "YcnrError", "_lib"]

@@ -52,7 +52,7 @@ EXPORTS = [
     "ycnr_comm_unique_id", "ycnr_als_comm_init", "ycnr_als_comm_destroy", "ycnr_als_set_ratings_sharded",
     "ycnr_als_exchange", "ycnr_als_broadcast_factors", "ycnr_als_allreduce_sum", "ycnr_als_comm_selftest",
     "ycnr_als_comm_info", "ycnr_als_last_rmse_ms", "ycnr_als_set_ratings_banded", "ycnr_als_defer_exchange",
-    "ycnr_als_step_implicit", "ycnr_als_step_implicit_cg",
+    "ycnr_als_step_implicit", "ycnr_als_step_implicit_cg", "ycnr_als_rank_eval",
 ]
 COMM_NONE, COMM_RCCL, COMM_SHM, COMM_IPC, COMM_STUB = 0, 1, 2, 3, 4
 COMM_ID_BYTES = 128
@@ -172,6 +172,8 @@ def load():
     L.ycnr_als_step_implicit.argtypes = [vp, i32, dbl, C.POINTER(C.c_int32), vp]
     L.ycnr_als_step_implicit_cg.restype = i32
     L.ycnr_als_step_implicit_cg.argtypes = [vp, i32, dbl, i32, C.POINTER(C.c_int32), vp]
+    L.ycnr_als_rank_eval.restype = i32
+    L.ycnr_als_rank_eval.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(dbl)]
     L.ycnr_csr_transpose.restype = i32
     L.ycnr_csr_transpose.argtypes = [i32, i64, i64, vp, vp, vp, vp, vp, vp, C.POINTER(dbl)]
     L.ycnr_comm_unique_id.restype = i32

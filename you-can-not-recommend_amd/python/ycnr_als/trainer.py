@@ -395,6 +395,29 @@ class AlsDevice:
                                          pred.ctypes.data, cnt.ctypes.data, C.byref(ms)))
         return ids, pred, cnt, ms.value
 
+    def rank_eval(self, userIds, testPtr, testIds, skipPtr, skipIds):
+        """Ranks of held-out items in each request user's ranking of the catalogue (ycnr_als_rank_eval): userIds / skipPtr /
+        skipIds as for recommend() (the skip list is the user's training items), testPtr / testIds the CSR of held-out item
+        ids, relative to the request, strictly ascending per user.  Returns (ranks [one per held-out pair]: the competing items
+        placed ahead of it, -1 where the item is in the user's own skip list; candidates [one per user]: the items that
+        compete; kernel ms).  ranking_metrics() turns them into the usual measures."""
+        uid = np.ascontiguousarray(userIds, np.int32).reshape(-1)
+        tp = np.ascontiguousarray(testPtr, np.int64).reshape(-1)
+        ti = np.ascontiguousarray(testIds, np.int32).reshape(-1)
+        sp = np.ascontiguousarray(skipPtr, np.int64).reshape(-1)
+        sk = np.ascontiguousarray(skipIds, np.int32).reshape(-1)
+        n = len(uid)
+        if len(tp) != n + 1 or len(sp) != n + 1:
+            raise ValueError("testPtr and skipPtr need one entry per requested user plus one")
+        if tp[-1] > len(ti) or sp[-1] > len(sk):
+            raise ValueError("testPtr / skipPtr run past their id arrays")
+        ranks = np.zeros(max(int(tp[-1]), 0), np.int32)
+        cand = np.zeros(n, np.int32)
+        ms = C.c_double(0.0)
+        check(self._L.ycnr_als_rank_eval(self._h, n, uid.ctypes.data, tp.ctypes.data, ti.ctypes.data if len(ti) else None, sp.ctypes.data,
+                                         sk.ctypes.data if len(sk) else None, ranks.ctypes.data, cand.ctypes.data, C.byref(ms)))
+        return ranks, cand, ms.value
+
     def _request_csr(self, rowPtr, indx, vals):
         rp = np.ascontiguousarray(rowPtr, np.int64).reshape(-1)
         ix = np.ascontiguousarray(indx, np.int32).reshape(-1)
