@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define YCNR_ALS_ABI_VERSION 4 /* 4: + ycnr_als_comm_info, ycnr_als_last_rmse_ms (nothing changed or removed); later, still 4: + ycnr_als_recommend, + ycnr_als_fold_in, ycnr_als_recommend_for_ratings; later, still 4: + ycnr_als_step_implicit; later, still 4: + ycnr_als_step_implicit_cg; later, still 4: + ycnr_als_rank_eval */
+#define YCNR_ALS_ABI_VERSION 4 /* 4: + ycnr_als_comm_info, ycnr_als_last_rmse_ms (nothing changed or removed); later, still 4: + ycnr_als_recommend, + ycnr_als_fold_in, ycnr_als_recommend_for_ratings; later, still 4: + ycnr_als_step_implicit; later, still 4: + ycnr_als_step_implicit_cg; later, still 4: + ycnr_als_rank_eval; later, still 4: + ycnr_als_fold_in_implicit, ycnr_als_recommend_for_observations */
 
 /* error codes */
 #define YCNR_OK 0
@@ -507,7 +507,8 @@ int ycnr_als_recommend_for_ratings(ycnr_als *h, int64_t nUsers, const int64_t *r
  *   msOut3    (may be NULL) {gramMs, rowsMs, totalMs}: G and its reduction, the row kernels, both -- from HIP events.
  * Enqueued on the handle's stream behind anything queued there; returns after the stream has drained.  G is summed in float64
  * in an order that depends on the fixed side's row count alone; every row is solved in float64 from its own sums (accumulated
- * in the handle's precision) and rounded once.  ycnr_als_recommend and, for the explicit model, fold-in serve the result unchanged.
+ * in the handle's precision) and rounded once.  ycnr_als_recommend serves the result unchanged; ycnr_als_fold_in_implicit and
+ * ycnr_als_recommend_for_observations (below) give rows of this model to users and items that were not trained.
  * YCNR_ERR_INVALID: null handle, bad side, alpha negative or not finite.  YCNR_ERR_STATE: no ratings for the side; half-steps
  * enqueued with ycnr_als_step_async and not yet completed by ycnr_als_sync.  YCNR_ERR_UNSUPPORTED: factorsCount > 128, a
  * communicator with world > 1, a banded side, a side uploaded in more than one piece.  The matrices are untouched then. */
@@ -536,6 +537,50 @@ int ycnr_als_step_implicit(ycnr_als *h, int side, double alpha, int32_t *badRows
  * Refusals as ycnr_als_step_implicit, and YCNR_ERR_INVALID for cgSteps < 1 or > 64.  The matrices are untouched then. */
 int ycnr_als_step_implicit_cg(ycnr_als *h, int side, double alpha, int32_t cgSteps, int32_t *badRows /* may be NULL */,
                               double *msOut3 /* may be NULL */);
+
+/* ---- Fold-in for the implicit model: rows solved from observations given in the call ------------------
+ *
+ * ycnr_als_fold_in solves the explicit normal equations (lambda n on the diagonal, no shared Gramian).  A model trained with
+ * ycnr_als_step_implicit needs the implicit row instead, and its typical newcomer has watched a handful of titles and rated none.
+ * For one request row with observations S (n of them), raw values r, w = alpha r, c = 1 + w, Y = ALL rows of the fixed matrix:
+ *     M = Y^T Y + lambda I            lambda: the side's userFactReg / itemFactReg, used PLAIN, as in ycnr_als_step_implicit
+ *     A = M + Y_S^T diag(w) Y_S,      x = A^-1 Y_S^T c                       (the row ycnr_als_step_implicit computes)
+ * M is shared by every row of the call: it is computed (the Gramian kernels of the half-step), factorised M = L L^T and inverted,
+ * Linv = L^-1, ONCE per call, all in float64.  A row with n <= 32, n <= factorsCount and every r >= 0 is then solved in DUAL
+ * (Woodbury) form, an n x n system instead of a k x k one (csrc/foldin_implicit_kernels.hip.h):
+ *     P = Linv Y_S^T (k x n);   K = P^T P = Y_S M^-1 Y_S^T;   D = diag(sqrt(w))
+ *     (I + D K D) y = D K c     symmetric, eigenvalues >= 1; nothing divides by w, so r = 0 is served
+ *     v = c - D y;              x = Linv^T (P v), rounded once to the handle's type
+ * Every other non-empty row (n > 32, n > factorsCount, or a value with !(r >= 0)) takes the exact k x k solve of
+ * ycnr_als_step_implicit (its row kernel, unchanged).  Which way a row goes depends on the row alone, and every sum's order is
+ * fixed by the row alone: a row's bits do not depend on what else the request holds.  All arithmetic of the dual rows is float64
+ * for both handle types.  G is recomputed in every call (a matrix bound with ycnr_als_bind_factors can change behind the handle's
+ * back; nothing is cached).
+ *   side, rowPtr, indx, vals, storeIds, outRows   as for ycnr_als_fold_in
+ *   alpha      the confidence weight of ycnr_als_step_implicit
+ *   flags      0, or YCNR_FOLD_PRIMAL_ONLY: every row by the exact k x k solve (A/B runs, tests)
+ *   outStatus  per row: 0 solved; 1 a pivot p with !(p > 0): the row is all zeros -- in the row's own system (NaN / Inf input, or
+ *              negative values that make A indefinite), or in M itself, and then for EVERY non-empty row of the call; 2 the row
+ *              has no observations: all zeros, nothing solved.  A non-zero status is NOT an error return.  (The k x k kernel
+ *              zeroes a row it cannot solve without naming it: such a row is recognised by being all zeros while the call's
+ *              count of failed rows is not zero.)
+ *   msOut3     (may be NULL) {G, its reduce and Linv; the row kernels and the finish; both} from HIP events on the handle's stream
+ * YCNR_ERR_INVALID (outputs and matrices untouched): what ycnr_als_fold_in refuses, alpha negative or not finite, unknown flag
+ * bits.  YCNR_ERR_UNSUPPORTED: factorsCount > 128 (there is no implicit path beyond).  nRows == 0 is YCNR_OK.
+ * Enqueued on the handle's stream behind the half-steps in flight, returns with the results on the host; the device buffers stay
+ * with the handle (a second call of the same size allocates nothing).  LOCAL, not collective.
+ *
+ * ycnr_als_recommend_for_observations: ycnr_als_recommend_for_ratings with this fold-in of the user side in front of the same
+ * top-N kernels: obsPtr / obsIds / obsVals are the request's observations; everything else as there.  Users with a non-zero
+ * status get outCount = 0. */
+#define YCNR_FOLD_PRIMAL_ONLY 1 /* flags: every row by the exact k x k solve */
+int ycnr_als_fold_in_implicit(ycnr_als *h, int side, double alpha, int64_t nRows, const int64_t *rowPtr, const int32_t *indx,
+                              const void *vals, const int32_t *storeIds /* may be NULL */, int32_t flags, void *outRows,
+                              int32_t *outStatus, double *msOut3 /* may be NULL: {G + factor, rows, total} */);
+int ycnr_als_recommend_for_observations(ycnr_als *h, double alpha, int64_t nUsers, const int64_t *obsPtr, const int32_t *obsIds,
+                                        const void *obsVals, const int64_t *skipPtr, const int32_t *skipIds, double globalAvgShift,
+                                        double minRecommendRating, int32_t limit, int32_t flags, int32_t *outIds, double *outPredict,
+                                        int32_t *outCount, void *outRows /* may be NULL */, int32_t *outStatus, double *deviceMs);
 
 /* ---- Ranking evaluation: where the model places held-out items -------------------------------------
  *

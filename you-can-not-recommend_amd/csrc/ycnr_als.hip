@@ -19,6 +19,7 @@
 #include "recommend_kernels.hip.h"
 #include "rank_kernels.hip.h"
 #include "foldin_kernels.hip.h"
+#include "foldin_implicit_kernels.hip.h"
 #include "implicit_kernels.hip.h"
 #include "implicit_cg_kernels.hip.h"
 
@@ -811,6 +812,9 @@ struct ycnr_als {
          // ycnr_als_fold_in / ycnr_als_recommend_for_ratings: the request's CSR, the solved rows and their status, the ids to store at;
          // factorsCount > 128: the plan of the step kernels (units, split rows, slabs) and their error record
          FOLD_PTR, FOLD_INDX, FOLD_VALS, FOLD_ROWS, FOLD_STATUS, FOLD_STORE, FOLD_UNITS, FOLD_SPLIT, FOLD_SLABS, FOLD_ERR, FOLD_PAD,
+         // ycnr_als_fold_in_implicit / ycnr_als_recommend_for_observations: L^-1 of G + lambda I, the dual rows, {bad rows, bad factor}
+         // (the request, the solved rows and the primal units go through the FOLD_* buffers above)
+         FOLD_LINV, FOLD_DUAL, FOLD_FLAGS,
          // ycnr_als_rank_eval: the slots, the held-out ids, a batch's histogram image, target order and skip marks, the two outputs
          RANK_SLOTS, RANK_TEST, RANK_HIST, RANK_ORDER, RANK_MARK, RANK_OUT, RANK_CAND, REC_NBUF };
   GrowBuf<ExactAlloc> rec[REC_NBUF];
@@ -824,6 +828,8 @@ struct ycnr_als {
     Event ev[3];
   } implicit;
   PiecePlan foldPlan;  // ycnr_als_fold_in beyond 128 factors: the plan whose lists are being copied to the device
+  FoldCut foldCut;     // ycnr_als_fold_in_implicit: the lists of the request being copied to the device (foldin_plan.h)
+  Event foldEv;        // ... and the event between its shared part (G, L^-1) and its rows
   DevPtr<ErrInfo> dErr;
   // The error record is never reset on the device: its count only grows, the host remembers what it has seen
   // (errSeen) and gets the record through an 8-byte copy into page-locked memory at the end of every half-step
@@ -2840,6 +2846,106 @@ int fold_enqueue_any(ycnr_als *h, int side, int64_t nRows, const int64_t *rowPtr
   return h->opt.dtype == YCNR_F64 ? fold_enqueue<double>(h, side, nRows, rowPtr, indx, vals, storeIds)
                                   : fold_enqueue<float>(h, side, nRows, rowPtr, indx, vals, storeIds);
 }
+
+// ---- implicit fold-in (foldin_implicit_kernels.hip.h, foldin_plan.h) ----
+
+// what ycnr_als_fold_in_implicit / ycnr_als_recommend_for_observations refuse beyond fold_check
+int fold_implicit_check(const char *what, const ycnr_als *h, double alpha, int32_t flags) {
+  if (!(alpha >= 0.0) || !std::isfinite(alpha)) return fail(YCNR_ERR_INVALID, "%s: alpha must be finite and >= 0", what);
+  if (flags & ~YCNR_FOLD_PRIMAL_ONLY) return fail(YCNR_ERR_INVALID, "%s: unknown flag bits 0x%x", what, (unsigned)flags);
+  if (h->opt.factorsCount > kFoldImplicitMaxK)
+    return fail(YCNR_ERR_UNSUPPORTED, "%s: factorsCount %d > %d", what, h->opt.factorsCount, kFoldImplicitMaxK);
+  return YCNR_OK;
+}
+
+// Uploads the (validated) request and enqueues G -> its reduce -> L^-1 -> the dual rows -> the primal units -> finish on the handle's
+// stream; records recEv[0] in front of the kernels and foldEv behind the part every row shares.  Afterwards FOLD_ROWS holds
+// nRows x factorsCount solved rows and FOLD_STATUS their status, both on the device.  G is computed anew in every call: a bound
+// matrix can change behind the handle's back, and the handle keeps no rule that would tell.
+template <typename T>
+int fold_implicit_enqueue(ycnr_als *h, int side, double alpha, int64_t nRows, const int64_t *rowPtr, const int32_t *indx, const void *vals,
+                          const int32_t *storeIds, int32_t flags) {
+  typedef ycnr_als A;
+  ycnr_als::Implicit &I = h->implicit;
+  const int k = h->opt.factorsCount, nb = (k + 15) / 16, kp = nb * 16, nt = tile_count(nb);
+  const int64_t total = rowPtr[nRows];
+  const int64_t m = h->rows(1 - side), sliceRows = implicit_slice_rows(m), nSlices = (m + sliceRows - 1) / sliceRows;
+  const double lambda = side == YCNR_BY_USER ? h->opt.userFactReg : h->opt.itemFactReg;
+  const T *fixed = (const T *)h->factors[1 - side];
+  FoldCut &cut = h->foldCut;  // (kept on the handle: its lists are the source of the copies below)
+  fold_cut<T>(nRows, rowPtr, (const T *)vals, k, (flags & YCNR_FOLD_PRIMAL_ONLY) != 0, cut);
+  const size_t nDual = cut.dual.size(), nPrimal = cut.primal.size();
+  HIP_TRY(h->rec[A::FOLD_PTR].reserve((size_t)(nRows + 1) * 8));
+  HIP_TRY(h->rec[A::FOLD_INDX].reserve(std::max<size_t>((size_t)total * 4 + 64, 8)));
+  HIP_TRY(h->rec[A::FOLD_VALS].reserve(std::max<size_t>((size_t)total * sizeof(T) + 64, 8)));
+  HIP_TRY(h->rec[A::FOLD_ROWS].reserve((size_t)nRows * k * sizeof(T)));
+  HIP_TRY(h->rec[A::FOLD_STATUS].reserve((size_t)nRows * 4));
+  if (storeIds) HIP_TRY(h->rec[A::FOLD_STORE].reserve((size_t)nRows * 4));
+  HIP_TRY(h->rec[A::FOLD_LINV].reserve((size_t)kp * kp * sizeof(double)));
+  HIP_TRY(h->rec[A::FOLD_DUAL].reserve(std::max<size_t>(nDual, 1) * 4));
+  HIP_TRY(h->rec[A::FOLD_UNITS].reserve(std::max<size_t>(nPrimal, 1) * sizeof(Unit)));
+  HIP_TRY(h->rec[A::FOLD_FLAGS].reserve(2 * sizeof(int32_t)));
+  HIP_TRY(I.gram.reserve((size_t)kp * kp * sizeof(double)));
+  HIP_TRY(I.partial.reserve((size_t)nSlices * nt * 256 * sizeof(double)));
+  for (Event &ev : h->recEv)
+    if (!ev) HIP_TRY(hipEventCreate(ev.put()));
+  if (!h->foldEv) HIP_TRY(hipEventCreate(h->foldEv.put()));
+  const size_t gramLds = implicit_gram_lds_bytes(k), unitLds = implicit_unit_lds_bytes(k, sizeof(T)), facLds = fold_factor_lds_bytes(k),
+               dualLds = fold_dual_lds_bytes(k);
+  if (int rc = set_max_lds(reinterpret_cast<const void *>(foldin_factor_kernel), facLds)) return rc;
+  if (int rc = set_max_lds(reinterpret_cast<const void *>(foldin_implicit_dual_kernel<T>), dualLds)) return rc;
+  if (int rc = set_max_lds(reinterpret_cast<const void *>(implicit_unit_kernel<T>), unitLds)) return rc;
+  // everything below is enqueued on the handle's stream: behind the half-steps in flight, like ycnr_als_fold_in
+  HIP_TRY(hipMemcpyAsync(h->rec[A::FOLD_PTR].get(), rowPtr, (size_t)(nRows + 1) * 8, hipMemcpyHostToDevice, h->stream));
+  if (total) {
+    HIP_TRY(hipMemcpyAsync(h->rec[A::FOLD_INDX].get(), indx, (size_t)total * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->rec[A::FOLD_VALS].get(), vals, (size_t)total * sizeof(T), hipMemcpyHostToDevice, h->stream));
+  }
+  if (storeIds) HIP_TRY(hipMemcpyAsync(h->rec[A::FOLD_STORE].get(), storeIds, (size_t)nRows * 4, hipMemcpyHostToDevice, h->stream));
+  if (nDual) HIP_TRY(hipMemcpyAsync(h->rec[A::FOLD_DUAL].get(), cut.dual.data(), nDual * 4, hipMemcpyHostToDevice, h->stream));
+  if (nPrimal) HIP_TRY(hipMemcpyAsync(h->rec[A::FOLD_UNITS].get(), cut.primal.data(), nPrimal * sizeof(Unit), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemsetAsync(h->rec[A::FOLD_STATUS].get(), 0xff, (size_t)nRows * 4, h->stream));  // -1: no dual kernel has solved the row
+  HIP_TRY(hipMemsetAsync(h->rec[A::FOLD_FLAGS].get(), 0, 2 * sizeof(int32_t), h->stream));
+  HIP_TRY(hipEventRecord(h->recEv[0].get(), h->stream));
+  double *G = (double *)I.gram.get(), *partial = (double *)I.partial.get(), *Linv = (double *)h->rec[A::FOLD_LINV].get();
+  int32_t *devFlags = (int32_t *)h->rec[A::FOLD_FLAGS].get();
+  const bool vec = k % (int)(16 / sizeof(T)) == 0 && (reinterpret_cast<uintptr_t>(fixed) & 15) == 0;
+  if (vec)
+    hipLaunchKernelGGL((implicit_gram_kernel<T, true>), dim3((unsigned)nSlices), dim3(256), gramLds, h->stream, fixed, m, k, sliceRows, partial);
+  else
+    hipLaunchKernelGGL((implicit_gram_kernel<T, false>), dim3((unsigned)nSlices), dim3(256), gramLds, h->stream, fixed, m, k, sliceRows, partial);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(implicit_gram_reduce_kernel, dim3((unsigned)nt), dim3(256), 0, h->stream, (const double *)partial, (int)nSlices, k, G, devFlags);
+  HIP_TRY(hipGetLastError());
+  if (nDual) {  // (without dual rows nothing reads L^-1, and flags[1] stays 0)
+    hipLaunchKernelGGL(foldin_factor_kernel, dim3(1), dim3(256), facLds, h->stream, (const double *)G, lambda, k, Linv, devFlags);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipEventRecord(h->foldEv.get(), h->stream));
+  T *rows = (T *)h->rec[A::FOLD_ROWS].get();
+  int32_t *status = (int32_t *)h->rec[A::FOLD_STATUS].get();
+  if (nDual) {
+    FoldDualArgs<T> d{(const int32_t *)h->rec[A::FOLD_DUAL].get(), (const int64_t *)h->rec[A::FOLD_PTR].get(), (const int32_t *)h->rec[A::FOLD_INDX].get(),
+                      (const T *)h->rec[A::FOLD_VALS].get(), fixed, (const double *)Linv, rows, status, alpha, k};
+    hipLaunchKernelGGL(foldin_implicit_dual_kernel<T>, dim3((unsigned)nDual), dim3(256), dualLds, h->stream, d);
+    HIP_TRY(hipGetLastError());
+  }
+  if (nPrimal) {
+    ImplicitArgs<T> a{(const Unit *)h->rec[A::FOLD_UNITS].get(), nullptr, (const int32_t *)h->rec[A::FOLD_INDX].get(), (const T *)h->rec[A::FOLD_VALS].get(),
+                      fixed, rows, (const double *)G, nullptr, devFlags, alpha, lambda, k};
+    hipLaunchKernelGGL(implicit_unit_kernel<T>, dim3((unsigned)nPrimal), dim3(256), unitLds, h->stream, a);
+    HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(foldin_implicit_finish_kernel<T>, dim3((unsigned)nRows), dim3(256), 0, h->stream, (const int64_t *)h->rec[A::FOLD_PTR].get(),
+                     (const int32_t *)devFlags, k, rows, status, storeIds ? (T *)h->factors[side] : nullptr, (const int32_t *)h->rec[A::FOLD_STORE].get());
+  HIP_TRY(hipGetLastError());
+  return YCNR_OK;
+}
+int fold_implicit_enqueue_any(ycnr_als *h, int side, double alpha, int64_t nRows, const int64_t *rowPtr, const int32_t *indx, const void *vals,
+                              const int32_t *storeIds, int32_t flags) {
+  return h->opt.dtype == YCNR_F64 ? fold_implicit_enqueue<double>(h, side, alpha, nRows, rowPtr, indx, vals, storeIds, flags)
+                                  : fold_implicit_enqueue<float>(h, side, alpha, nRows, rowPtr, indx, vals, storeIds, flags);
+}
 }  // namespace
 }  // extern "C++"
 
@@ -2906,6 +3012,63 @@ int ycnr_als_recommend_for_ratings(ycnr_als *h, int64_t nUsers, const int64_t *r
   typedef ycnr_als A;
   const size_t rowBytes = (size_t)nUsers * h->opt.factorsCount * h->ts();
   // the solved rows never leave the device between the two halves; their copy to the host rides behind the top-N
+  auto copies = [&]() -> int {
+    if (outRows) HIP_TRY(hipMemcpyAsync(outRows, h->rec[A::FOLD_ROWS].get(), rowBytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(outStatus, h->rec[A::FOLD_STATUS].get(), (size_t)nUsers * 4, hipMemcpyDeviceToHost, h->stream));
+    return YCNR_OK;
+  };
+  return recommend_run(h, h->rec[A::FOLD_ROWS].get(), nUsers, nullptr, skipPtr, skipIds, globalAvgShift, minRecommendRating, limit, outIds, outPredict,
+                       outCount, deviceMs, true, (const int32_t *)h->rec[A::FOLD_STATUS].get(), copies);
+}
+
+int ycnr_als_fold_in_implicit(ycnr_als *h, int side, double alpha, int64_t nRows, const int64_t *rowPtr, const int32_t *indx, const void *vals,
+                              const int32_t *storeIds, int32_t flags, void *outRows, int32_t *outStatus, double *msOut3) {
+  if (!h) return fail(YCNR_ERR_INVALID, "null handle");
+  if (side != YCNR_BY_USER && side != YCNR_BY_ITEM) return fail(YCNR_ERR_INVALID, "bad side %d", side);
+  if (nRows < 0 || nRows > 0x7fffffffLL) return fail(YCNR_ERR_INVALID, "ycnr_als_fold_in_implicit: bad nRows");
+  if (int rc = fold_implicit_check("ycnr_als_fold_in_implicit", h, alpha, flags)) return rc;
+  if (nRows == 0) {
+    if (msOut3) msOut3[0] = msOut3[1] = msOut3[2] = 0.0;
+    return YCNR_OK;
+  }
+  if (!outRows || !outStatus) return fail(YCNR_ERR_INVALID, "ycnr_als_fold_in_implicit: null argument");
+  if (int rc = fold_check("ycnr_als_fold_in_implicit", h, side, nRows, rowPtr, indx, vals, storeIds)) return rc;
+  HIP_TRY(hipSetDevice(h->opt.device));
+  if (int rc = fold_implicit_enqueue_any(h, side, alpha, nRows, rowPtr, indx, vals, storeIds, flags)) return rc;
+  typedef ycnr_als A;
+  HIP_TRY(hipEventRecord(h->recEv[1].get(), h->stream));
+  HIP_TRY(hipMemcpyAsync(outRows, h->rec[A::FOLD_ROWS].get(), (size_t)nRows * h->opt.factorsCount * h->ts(), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(outStatus, h->rec[A::FOLD_STATUS].get(), (size_t)nRows * 4, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (msOut3) {
+    float g = 0, r = 0, t = 0;
+    HIP_TRY(hipEventElapsedTime(&g, h->recEv[0].get(), h->foldEv.get()));
+    HIP_TRY(hipEventElapsedTime(&r, h->foldEv.get(), h->recEv[1].get()));
+    HIP_TRY(hipEventElapsedTime(&t, h->recEv[0].get(), h->recEv[1].get()));
+    msOut3[0] = g, msOut3[1] = r, msOut3[2] = t;
+  }
+  return YCNR_OK;
+}
+
+int ycnr_als_recommend_for_observations(ycnr_als *h, double alpha, int64_t nUsers, const int64_t *obsPtr, const int32_t *obsIds, const void *obsVals,
+                                        const int64_t *skipPtr, const int32_t *skipIds, double globalAvgShift, double minRecommendRating,
+                                        int32_t limit, int32_t flags, int32_t *outIds, double *outPredict, int32_t *outCount, void *outRows,
+                                        int32_t *outStatus, double *deviceMs) {
+  if (!h) return fail(YCNR_ERR_INVALID, "null handle");
+  if (nUsers < 0 || nUsers > 0x7fffffffLL || limit < 1 || limit > 4096)
+    return fail(YCNR_ERR_INVALID, "ycnr_als_recommend_for_observations: bad nUsers / limit");
+  if (int rc = fold_implicit_check("ycnr_als_recommend_for_observations", h, alpha, flags)) return rc;
+  if (nUsers == 0) {
+    if (deviceMs) *deviceMs = 0.0;
+    return YCNR_OK;
+  }
+  if (!skipPtr || !outIds || !outPredict || !outCount || !outStatus) return fail(YCNR_ERR_INVALID, "ycnr_als_recommend_for_observations: null argument");
+  if (int rc = fold_check("ycnr_als_recommend_for_observations", h, YCNR_BY_USER, nUsers, obsPtr, obsIds, obsVals, nullptr)) return rc;
+  if (int rc = check_skip_lists("ycnr_als_recommend_for_observations", nUsers, skipPtr, skipIds)) return rc;
+  HIP_TRY(hipSetDevice(h->opt.device));
+  if (int rc = fold_implicit_enqueue_any(h, YCNR_BY_USER, alpha, nUsers, obsPtr, obsIds, obsVals, nullptr, flags)) return rc;
+  typedef ycnr_als A;
+  const size_t rowBytes = (size_t)nUsers * h->opt.factorsCount * h->ts();
   auto copies = [&]() -> int {
     if (outRows) HIP_TRY(hipMemcpyAsync(outRows, h->rec[A::FOLD_ROWS].get(), rowBytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipMemcpyAsync(outStatus, h->rec[A::FOLD_STATUS].get(), (size_t)nUsers * 4, hipMemcpyDeviceToHost, h->stream));

@@ -465,3 +465,47 @@ class AlsDevice:
                                                      float(globalAvgShift), float(minRecommendRating), int(limit), ids.ctypes.data,
                                                      pred.ctypes.data, cnt.ctypes.data, rows.ctypes.data, status.ctypes.data, C.byref(ms)))
         return ids, pred, cnt, rows, status, ms.value
+
+    def fold_in_implicit(self, side, alpha, rowPtr, indx, vals, storeIds=None, primal_only=False):
+        """fold_in() for the implicit-feedback model (ycnr_als_fold_in_implicit): the rows step_implicit(side, alpha) would give
+        the request's observations against the fixed opposite matrix.  Rows of at most 32 non-negative observations are solved
+        in dual form from one factorisation of G + lambda I per call, the others exactly like the half-step; primal_only sends
+        every row the exact way.  Returns (rows [n x k], status [n]: 0 solved / 1 bad pivot / 2 no observations,
+        ms = np.array([G and factor, rows, total]))."""
+        rp, ix, vl = self._request_csr(rowPtr, indx, vals)
+        n = len(rp) - 1
+        st = None if storeIds is None else np.ascontiguousarray(storeIds, np.int32).reshape(-1)
+        if st is not None and len(st) != n:
+            raise ValueError("storeIds needs one id per request row")
+        rows = np.zeros((n, self.k), self.dtype)
+        status = np.zeros(n, np.int32)
+        ms = np.zeros(3, np.float64)
+        check(self._L.ycnr_als_fold_in_implicit(self._h, SIDES[side], float(alpha), n, rp.ctypes.data, ix.ctypes.data if len(ix) else None,
+                                                vl.ctypes.data if len(vl) else None, None if st is None else st.ctypes.data,
+                                                _lib.FOLD_PRIMAL_ONLY if primal_only else 0, rows.ctypes.data, status.ctypes.data,
+                                                ms.ctypes.data))
+        return rows, status, ms
+
+    def recommend_for_observations(self, alpha, obsPtr, obsIds, obsVals, skipPtr, skipIds, globalAvgShift=0.0, minRecommendRating=7.0,
+                                   limit=20, primal_only=False):
+        """fold_in_implicit('byUser', alpha) of the request's observations, then recommend() on the solved rows without a host
+        round trip (ycnr_als_recommend_for_observations).  Returns what recommend_for_ratings returns."""
+        rp, ix, vl = self._request_csr(obsPtr, obsIds, obsVals)
+        n = len(rp) - 1
+        sp = np.ascontiguousarray(skipPtr, np.int64)
+        sk = np.ascontiguousarray(skipIds, np.int32)
+        if len(sp) != n + 1:
+            raise ValueError("skipPtr needs one entry per requested user plus one")
+        ids = np.full((n, max(int(limit), 0)), -1, np.int32)
+        pred = np.zeros((n, max(int(limit), 0)), np.float64)
+        cnt = np.zeros(n, np.int32)
+        rows = np.zeros((n, self.k), self.dtype)
+        status = np.zeros(n, np.int32)
+        ms = C.c_double(0.0)
+        check(self._L.ycnr_als_recommend_for_observations(self._h, float(alpha), n, rp.ctypes.data, ix.ctypes.data if len(ix) else None,
+                                                          vl.ctypes.data if len(vl) else None, sp.ctypes.data,
+                                                          sk.ctypes.data if len(sk) else None, float(globalAvgShift),
+                                                          float(minRecommendRating), int(limit), _lib.FOLD_PRIMAL_ONLY if primal_only else 0,
+                                                          ids.ctypes.data, pred.ctypes.data, cnt.ctypes.data, rows.ctypes.data,
+                                                          status.ctypes.data, C.byref(ms)))
+        return ids, pred, cnt, rows, status, ms.value
