@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define YCNR_ALS_ABI_VERSION 4 /* 4: + ycnr_als_comm_info, ycnr_als_last_rmse_ms (nothing changed or removed); later, still 4: + ycnr_als_recommend, + ycnr_als_fold_in, ycnr_als_recommend_for_ratings; later, still 4: + ycnr_als_step_implicit; later, still 4: + ycnr_als_step_implicit_cg; later, still 4: + ycnr_als_rank_eval; later, still 4: + ycnr_als_fold_in_implicit, ycnr_als_recommend_for_observations */
+#define YCNR_ALS_ABI_VERSION 4 /* 4: + ycnr_als_comm_info, ycnr_als_last_rmse_ms (nothing changed or removed); later, still 4: + ycnr_als_recommend, + ycnr_als_fold_in, ycnr_als_recommend_for_ratings; later, still 4: + ycnr_als_step_implicit; later, still 4: + ycnr_als_step_implicit_cg; later, still 4: + ycnr_als_rank_eval; later, still 4: + ycnr_als_fold_in_implicit, ycnr_als_recommend_for_observations; later, still 4: + ycnr_als_step_implicit_sub */
 
 /* error codes */
 #define YCNR_OK 0
@@ -538,6 +538,38 @@ int ycnr_als_step_implicit(ycnr_als *h, int side, double alpha, int32_t *badRows
 int ycnr_als_step_implicit_cg(ycnr_als *h, int side, double alpha, int32_t cgSteps, int32_t *badRows /* may be NULL */,
                               double *msOut3 /* may be NULL */);
 
+/* The same half-step by 16-wide subspace solves, factorsCount <= 512: block coordinate descent on each row's quadratic, the
+ * subspace solver of iALS++ (Rendle, Krichene, Zhang, Koren 2021), warm-started from the row as it stands in the handle.  The
+ * way to train the implicit model beyond 128 factors, where a row's k x k image no longer fits on chip: the method's state per
+ * row is one k-vector and the largest system it solves is 16 x 16 (csrc/implicit_sub_kernels.hip.h).
+ * Notation is that of ycnr_als_step_implicit:
+ * - Y = all m rows of the fixed matrix, G = Y^T Y, lambda plain.
+ * - For a row of the shard: S = its observations, r_i = raw values, w_i = alpha r_i, c_i = 1 + w_i.
+ * - B = ceil(k / 16) blocks.  pi_b = coordinates 16b ... min(16b + 15, k - 1).
+ *     x = the row as it stands;   e_i = y_i . x   for i in S
+ *     repeat `sweeps` times, for b = 0 .. B-1 in order:
+ *         g = (G x)_pi + lambda x_pi + sum_i (w_i e_i - c_i) y_i,pi
+ *         H = G_pipi + lambda I + sum_i w_i y_i,pi y_i,pi^T
+ *         delta = H^-1 g  (L D L^T);   a pivot p with !(p > 0): the row is bad
+ *         x_pi -= delta;   e_i -= y_i,pi . delta   for i in S
+ *     store x, rounded once to the handle's type
+ * Numerical and data rules:
+ * - x, e, g, H, delta and every sum are float64 for both handle types.
+ * - Every sum's order depends on (m, the row) alone, so the same request gives the same bits whatever the grid.
+ * - Rows of the shard without observations become zeros.  Rows outside the shard are untouched.
+ * - Padded coordinates of the last block get a unit pivot and a zero gradient.  They never move.
+ * - Bad rows, including a result that is not finite, become zeros and are counted in badRows.  The call still returns YCNR_OK.
+ * Per sweep a row of n observations costs about 2 n k multiply-adds for scores and gradients, 8 n k for the sixteen-wide
+ * Hessians and k^2 for its share of the product with G; the exact solve costs n k^2 + k^3 / 3.  Every row is kept whole,
+ * whatever options.chunkRatings says.  The scores e live in a scratch buffer of the handle, 8 bytes per rating of the side.
+ *   sweeps    1 .. 16
+ *   msOut3    (may be NULL) {G and its reduce, the row kernels, both}
+ * For factorsCount <= 128, G is computed by the kernels of ycnr_als_step_implicit and has the bits that entry sees.
+ * Refusals as ycnr_als_step_implicit -- except that factorsCount may be up to 512 (beyond: YCNR_ERR_UNSUPPORTED) -- and
+ * YCNR_ERR_INVALID for sweeps < 1 or > 16.  The matrices are untouched then.  The fold-in entries below still stop at 128. */
+int ycnr_als_step_implicit_sub(ycnr_als *h, int side, double alpha, int32_t sweeps, int32_t *badRows /* may be NULL */,
+                               double *msOut3 /* may be NULL */);
+
 /* ---- Fold-in for the implicit model: rows solved from observations given in the call ------------------
  *
  * ycnr_als_fold_in solves the explicit normal equations (lambda n on the diagonal, no shared Gramian).  A model trained with
@@ -566,7 +598,7 @@ int ycnr_als_step_implicit_cg(ycnr_als *h, int side, double alpha, int32_t cgSte
  *              count of failed rows is not zero.)
  *   msOut3     (may be NULL) {G, its reduce and Linv; the row kernels and the finish; both} from HIP events on the handle's stream
  * YCNR_ERR_INVALID (outputs and matrices untouched): what ycnr_als_fold_in refuses, alpha negative or not finite, unknown flag
- * bits.  YCNR_ERR_UNSUPPORTED: factorsCount > 128 (there is no implicit path beyond).  nRows == 0 is YCNR_OK.
+ * bits.  YCNR_ERR_UNSUPPORTED: factorsCount > 128 (beyond it only ycnr_als_step_implicit_sub trains the implicit model; there is no fold-in).  nRows == 0 is YCNR_OK.
  * Enqueued on the handle's stream behind the half-steps in flight, returns with the results on the host; the device buffers stay
  * with the handle (a second call of the same size allocates nothing).  LOCAL, not collective.
  *

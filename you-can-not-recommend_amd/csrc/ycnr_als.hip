@@ -22,6 +22,7 @@
 #include "foldin_implicit_kernels.hip.h"
 #include "implicit_kernels.hip.h"
 #include "implicit_cg_kernels.hip.h"
+#include "implicit_sub_kernels.hip.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -719,12 +720,20 @@ struct ImplicitPlan {
   DevPtr<SplitRow> dSplit;
   DevPtr<int32_t> dEmpty;  // rows of the piece without observations
 };
+// ... and that of ycnr_als_step_implicit_sub: every non-empty row whole, longest first (ties in row order), and the empty rows
+struct ImplicitSubPlan {
+  bool built = false;
+  int64_t nRows = 0, nEmpty = 0;
+  DevPtr<Unit> dRows;
+  DevPtr<int32_t> dEmpty;
+};
 
 struct Part {
   Ratings R;
   Schedule S;
   std::vector<int64_t> hostPtr;  // the piece's row pointer as uploaded (8 bytes per row): what ImplicitPlan is built from
   ImplicitPlan implicit;
+  ImplicitSubPlan implicitSub;
   Event ev[5], ready, x0, x1;
   // fork / join of the piece's dual-class launches on the handle's side streams, and "all kernels of the piece done":
   // per piece, because two pieces are in flight at a time (on the handle's two piece streams)
@@ -820,9 +829,9 @@ struct ycnr_als {
   GrowBuf<ExactAlloc> rec[REC_NBUF];
   Event recEv[2];
   // ycnr_als_step_implicit: G, its per-slice partials and the slabs of split rows (grow-only: a second half-step of the same size
-  // allocates nothing), the bad-row count and the three timing events
+  // allocates nothing), the bad-row count and the three timing events; scores: ycnr_als_step_implicit_sub, a double per rating
   struct Implicit {
-    GrowBuf<ExactAlloc> gram, partial, slabs;
+    GrowBuf<ExactAlloc> gram, partial, slabs, scores;
     DevPtr<int32_t> dBad;
     HostPtr<int32_t> hBad;
     Event ev[3];
@@ -1456,6 +1465,7 @@ static int build_part(ycnr_als *h, int side, const int64_t *rowPtr, const int32_
   part.S = std::move(S);
   part.hostPtr = std::move(hp);
   part.implicit = ImplicitPlan();
+  part.implicitSub = ImplicitSubPlan();
   return YCNR_OK;
 }
 
@@ -2471,6 +2481,126 @@ int ycnr_als_step_implicit(ycnr_als *h, int side, double alpha, int32_t *badRows
   if (!part.implicit.built)
     if (int rc = implicit_build_plan(part, h->autoChunk ? kImplicitChunk : h->opt.chunkRatings)) return rc;
   if (int rc = h->opt.dtype == YCNR_F64 ? implicit_enqueue<double>(h, side, part, alpha) : implicit_enqueue<float>(h, side, part, alpha)) return rc;
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (badRows) *badRows = *h->implicit.hBad.get();
+  if (msOut3) {
+    float g = 0, r = 0, t = 0;
+    HIP_TRY(hipEventElapsedTime(&g, h->implicit.ev[0].get(), h->implicit.ev[1].get()));
+    HIP_TRY(hipEventElapsedTime(&r, h->implicit.ev[1].get(), h->implicit.ev[2].get()));
+    HIP_TRY(hipEventElapsedTime(&t, h->implicit.ev[0].get(), h->implicit.ev[2].get()));
+    msOut3[0] = g, msOut3[1] = r, msOut3[2] = t;
+  }
+  return YCNR_OK;
+}
+
+// ---- the same half-step by 16-wide subspace solves (implicit_sub_kernels.hip.h) ----
+extern "C++" {
+namespace {
+// build_schedule, asked for a chunk longer than any row, yields every non-empty row whole, longest first, ties in row order
+int implicit_sub_build_plan(Part &part) {
+  ImplicitSubPlan N;
+  std::vector<Unit> rows;
+  std::vector<SplitRow> split;
+  std::vector<int32_t> empty;
+  int64_t nSlabs = 0, solved = 0;
+  const int64_t nRows = part.R.rowEnd - part.R.rowBegin;
+  build_schedule(part.hostPtr.data(), part.R.rowBegin, nRows, INT32_MAX, rows, split, nSlabs, solved, -1, INT32_MAX, kMaxSlabsPerRow);
+  if (!split.empty()) return fail(YCNR_ERR_UNSUPPORTED, "ycnr_als_step_implicit_sub: a row of more than %d observations", INT32_MAX);
+  for (int64_t r = 0; r < nRows; ++r)
+    if (part.hostPtr[(size_t)r + 1] == part.hostPtr[(size_t)r]) empty.push_back((int32_t)(part.R.rowBegin + r));
+  N.nRows = (int64_t)rows.size(), N.nEmpty = (int64_t)empty.size();
+  if (N.nRows) {
+    HIP_TRY(hipMalloc(N.dRows.put(), sizeof(Unit) * rows.size()));
+    HIP_TRY(hipMemcpy(N.dRows.get(), rows.data(), sizeof(Unit) * rows.size(), hipMemcpyHostToDevice));
+  }
+  if (N.nEmpty) {
+    HIP_TRY(hipMalloc(N.dEmpty.put(), sizeof(int32_t) * empty.size()));
+    HIP_TRY(hipMemcpy(N.dEmpty.get(), empty.data(), sizeof(int32_t) * empty.size(), hipMemcpyHostToDevice));
+  }
+  N.built = true;
+  part.implicitSub = std::move(N);
+  return YCNR_OK;
+}
+
+// gram -> gram-reduce (k <= 128: the kernels of ycnr_als_step_implicit, so that G has the bits its other entries see; beyond:
+// the wide pair) -> 16 whole rows per workgroup through all block steps -> zero rows, all on the handle's stream
+template <typename T>
+int implicit_sub_enqueue(ycnr_als *h, int side, Part &part, double alpha, int sweeps) {
+  ycnr_als::Implicit &I = h->implicit;
+  const ImplicitSubPlan &P = part.implicitSub;
+  const int k = h->opt.factorsCount, nb = (k + 15) / 16, kp = nb * 16, nt = tile_count(nb);
+  const bool wide = k > kImplicitMaxK;
+  const int nPairs = tile_count((k + 63) / 64);
+  const int64_t m = h->rows(1 - side), sliceRows = wide ? implicit_wide_slice_rows(m) : implicit_slice_rows(m),
+                nSlices = (m + sliceRows - 1) / sliceRows, nBatches = (P.nRows + kSubBatch - 1) / kSubBatch;
+  const T *fixed = (const T *)h->factors[1 - side];
+  HIP_TRY(I.gram.reserve((size_t)kp * kp * sizeof(double)));
+  HIP_TRY(I.partial.reserve((size_t)nSlices * (wide ? (size_t)nPairs * 4096 : (size_t)nt * 256) * sizeof(double)));
+  if (part.R.nnz) HIP_TRY(I.scores.reserve((size_t)part.R.nnz * sizeof(double)));
+  if (!I.dBad) HIP_TRY(hipMalloc(I.dBad.put(), sizeof(int32_t)));
+  if (!I.hBad) HIP_TRY(hipHostMalloc((void **)I.hBad.put(), sizeof(int32_t), hipHostMallocDefault));
+  for (Event &e : I.ev)
+    if (!e) HIP_TRY(hipEventCreate(e.put()));
+  double *G = (double *)I.gram.get(), *partial = (double *)I.partial.get();
+  const size_t subLds = implicit_sub_lds_bytes(k);
+  if (int rc = set_max_lds(reinterpret_cast<const void *>(implicit_sub_kernel<T>), subLds)) return rc;
+  HIP_TRY(hipEventRecord(I.ev[0].get(), h->stream));
+  if (wide) {
+    hipLaunchKernelGGL(implicit_gram_wide_kernel<T>, dim3((unsigned)nPairs, (unsigned)nSlices), dim3(256), 0, h->stream, fixed, m, k, sliceRows, partial);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(implicit_gram_wide_reduce_kernel, dim3((unsigned)nPairs * 16), dim3(256), 0, h->stream, (const double *)partial, (int)nSlices, k, G,
+                       I.dBad.get());
+  } else {
+    const bool vec = k % (int)(16 / sizeof(T)) == 0 && (reinterpret_cast<uintptr_t>(fixed) & 15) == 0;
+    const size_t gramLds = implicit_gram_lds_bytes(k);
+    if (vec)
+      hipLaunchKernelGGL((implicit_gram_kernel<T, true>), dim3((unsigned)nSlices), dim3(256), gramLds, h->stream, fixed, m, k, sliceRows, partial);
+    else
+      hipLaunchKernelGGL((implicit_gram_kernel<T, false>), dim3((unsigned)nSlices), dim3(256), gramLds, h->stream, fixed, m, k, sliceRows, partial);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(implicit_gram_reduce_kernel, dim3((unsigned)nt), dim3(256), 0, h->stream, (const double *)partial, (int)nSlices, k, G, I.dBad.get());
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(I.ev[1].get(), h->stream));
+  const double lambda = side == YCNR_BY_USER ? h->opt.userFactReg : h->opt.itemFactReg;
+  if (nBatches) {
+    ImplicitSubArgs<T> s{P.dRows.get(), P.nRows, part.R.dIndx.get(), (const T *)part.R.dVals.get(), fixed, (T *)h->factors[side],
+                         G, (double *)I.scores.get(), I.dBad.get(), alpha, lambda, k, sweeps};
+    hipLaunchKernelGGL(implicit_sub_kernel<T>, dim3((unsigned)nBatches), dim3(256), subLds, h->stream, s);
+    HIP_TRY(hipGetLastError());
+  }
+  if (P.nEmpty) {
+    hipLaunchKernelGGL(implicit_zero_rows_kernel<T>, dim3((unsigned)((P.nEmpty * k + 255) / 256)), dim3(256), 0, h->stream,
+                       (const int32_t *)P.dEmpty.get(), P.nEmpty, k, (T *)h->factors[side]);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipEventRecord(I.ev[2].get(), h->stream));
+  HIP_TRY(hipMemcpyAsync(I.hBad.get(), I.dBad.get(), sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  return YCNR_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int ycnr_als_step_implicit_sub(ycnr_als *h, int side, double alpha, int32_t sweeps, int32_t *badRows, double *msOut3) {
+  const char *who = "ycnr_als_step_implicit_sub";
+  if (sweeps < 1 || sweeps > kSubMaxSweeps) return fail(YCNR_ERR_INVALID, "%s: sweeps %d outside 1 .. %d", who, sweeps, kSubMaxSweeps);
+  if (!h) return fail(YCNR_ERR_INVALID, "null handle");
+  if (side != YCNR_BY_USER && side != YCNR_BY_ITEM) return fail(YCNR_ERR_INVALID, "bad side %d", side);
+  if (!(alpha >= 0.0) || !std::isfinite(alpha)) return fail(YCNR_ERR_INVALID, "%s: alpha must be finite and >= 0", who);
+  if (h->opt.factorsCount > kImplicitSubMaxK) return fail(YCNR_ERR_UNSUPPORTED, "%s: factorsCount %d > %d", who, h->opt.factorsCount, kImplicitSubMaxK);
+  std::vector<Part> &parts = h->parts[side];
+  if (parts.empty()) return fail(YCNR_ERR_STATE, "%s: set_ratings was not called for this side", who);
+  if (h->infoPending) return fail(YCNR_ERR_STATE, "%s: half-steps are in flight (ycnr_als_sync first)", who);
+  if (h->comm.active() && h->comm.world > 1) return fail(YCNR_ERR_UNSUPPORTED, "%s: not with a communicator of several ranks", who);
+  if (h->banded[side].on) return fail(YCNR_ERR_UNSUPPORTED, "%s: not for a banded side", who);
+  if (parts.size() != 1) return fail(YCNR_ERR_UNSUPPORTED, "%s: the side was uploaded in %zu pieces", who, parts.size());
+  HIP_TRY(hipSetDevice(h->opt.device));
+  Part &part = parts[0];
+  if (!part.implicitSub.built)
+    if (int rc = implicit_sub_build_plan(part)) return rc;
+  if (int rc = h->opt.dtype == YCNR_F64 ? implicit_sub_enqueue<double>(h, side, part, alpha, sweeps)
+                                        : implicit_sub_enqueue<float>(h, side, part, alpha, sweeps))
+    return rc;
   HIP_TRY(hipStreamSynchronize(h->stream));
   if (badRows) *badRows = *h->implicit.hBad.get();
   if (msOut3) {

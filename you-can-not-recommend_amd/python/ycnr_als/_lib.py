@@ -53,7 +53,7 @@ EXPORTS = [
     "ycnr_als_exchange", "ycnr_als_broadcast_factors", "ycnr_als_allreduce_sum", "ycnr_als_comm_selftest",
     "ycnr_als_comm_info", "ycnr_als_last_rmse_ms", "ycnr_als_set_ratings_banded", "ycnr_als_defer_exchange",
     "ycnr_als_step_implicit", "ycnr_als_step_implicit_cg", "ycnr_als_rank_eval",
-    "ycnr_als_fold_in_implicit", "ycnr_als_recommend_for_observations",
+    "ycnr_als_fold_in_implicit", "ycnr_als_recommend_for_observations", "ycnr_als_step_implicit_sub",
 ]
 FOLD_PRIMAL_ONLY = 1  # YCNR_FOLD_PRIMAL_ONLY
 COMM_NONE, COMM_RCCL, COMM_SHM, COMM_IPC, COMM_STUB = 0, 1, 2, 3, 4
@@ -174,6 +174,8 @@ def load():
     L.ycnr_als_step_implicit.argtypes = [vp, i32, dbl, C.POINTER(C.c_int32), vp]
     L.ycnr_als_step_implicit_cg.restype = i32
     L.ycnr_als_step_implicit_cg.argtypes = [vp, i32, dbl, i32, C.POINTER(C.c_int32), vp]
+    L.ycnr_als_step_implicit_sub.restype = i32
+    L.ycnr_als_step_implicit_sub.argtypes = [vp, i32, dbl, i32, C.POINTER(C.c_int32), vp]
     L.ycnr_als_rank_eval.restype = i32
     L.ycnr_als_rank_eval.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(dbl)]
     L.ycnr_als_fold_in_implicit.restype = i32

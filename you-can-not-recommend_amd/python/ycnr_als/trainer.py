@@ -324,15 +324,21 @@ class AlsDevice:
         check(self._L.ycnr_als_step(self._h, SIDES[side]))
         return self.last_step_info()
 
-    def step_implicit(self, side, alpha, cg_steps=None):
+    def step_implicit(self, side, alpha, cg_steps=None, sweeps=None):
         """One implicit-feedback half-step (Hu, Koren, Volinsky 2008; ycnr_als_step_implicit) of `side` from the ratings uploaded
         with set_ratings: confidence 1 + alpha r, the side's regularisation used plain; rows without observations become zeros.
         cg_steps: None solves every row exactly; an integer 1 .. 64 runs that many conjugate-gradient steps per row from the
         row as it stands (ycnr_als_step_implicit_cg; rows longer than a work unit's chunk are still solved exactly).
+        sweeps: an integer 1 .. 16 runs that many sweeps of 16-wide subspace solves per row from the row as it stands
+        (ycnr_als_step_implicit_sub: the one that serves factorsCount up to 512).  cg_steps and sweeps exclude each other.
         Returns (badRows, ms) with ms = np.array([gramMs, rowsMs, totalMs])."""
+        if cg_steps is not None and sweeps is not None:
+            raise ValueError("step_implicit: pass cg_steps or sweeps, not both")
         bad = C.c_int32(0)
         ms = np.zeros(3, np.float64)
-        if cg_steps is None:
+        if sweeps is not None:
+            check(self._L.ycnr_als_step_implicit_sub(self._h, SIDES[side], float(alpha), int(sweeps), C.byref(bad), ms.ctypes.data))
+        elif cg_steps is None:
             check(self._L.ycnr_als_step_implicit(self._h, SIDES[side], float(alpha), C.byref(bad), ms.ctypes.data))
         else:
             check(self._L.ycnr_als_step_implicit_cg(self._h, SIDES[side], float(alpha), int(cg_steps), C.byref(bad), ms.ctypes.data))
