@@ -531,8 +531,10 @@ int ycnr_als_step_implicit(ycnr_als *h, int side, double alpha, int32_t *badRows
  *   chunk (options.chunkRatings, else the library's 4096) are few and bound by their Gramian: they are solved exactly, by the
  *   kernels of ycnr_als_step_implicit.
  *   cgSteps   1 .. 64
- *   badRows   (may be NULL) rows whose stored result would not be finite (they become zeros), plus the exactly solved rows
- *             counted as above.
+ *   badRows   (may be NULL) rows whose stored result would not be finite, and rows that meet a rho or d that is not finite (a NaN
+ *             or Inf among the row's values, in its warm start or in G: the stop rule alone would leave the warm start standing
+ *             as if it were a result) -- they become zeros --, plus the exactly solved rows counted as above.  A negative r
+ *             that makes A indefinite is NOT counted here: the row follows the iteration above, its stop rule included.
  *   msOut3    as above; rowsMs covers the conjugate-gradient kernel and the exact kernels of the long rows.
  * Refusals as ycnr_als_step_implicit, and YCNR_ERR_INVALID for cgSteps < 1 or > 64.  The matrices are untouched then. */
 int ycnr_als_step_implicit_cg(ycnr_als *h, int side, double alpha, int32_t cgSteps, int32_t *badRows /* may be NULL */,

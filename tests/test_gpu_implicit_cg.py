@@ -19,7 +19,8 @@ LD = np.longdouble if np.finfo(np.longdouble).eps < EPS64 else np.float64
 SOLVED, SHARD, CHUNK, EMPTY = 36, (1, 35), 64, 6  # 32 whole rows with observations: two batches of 16, the second one short
 
 
-def cg_reference(alpha, lam, G, Ys, r, x, steps):
+def cg_reference(alpha, lam, G, Ys, r, x, steps, trace=None):
+    """trace: a list that receives (d, p . p) of every step the row takes (tests/test_gpu_implicit_edges.py checks d's margin)"""
     w = alpha * r
     op = lambda v: G @ v + lam * v + Ys.T @ (w * (Ys @ v))
     res = Ys.T @ (1 + w) - op(x)
@@ -27,6 +28,8 @@ def cg_reference(alpha, lam, G, Ys, r, x, steps):
     for _ in range(steps):
         q = op(p)
         d = p @ q
+        if trace is not None:
+            trace.append((d, p @ p))
         if rho == 0 or not d > 0:
             break
         a = rho / d

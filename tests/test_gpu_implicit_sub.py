@@ -19,11 +19,14 @@ WIDE = 256  # kSubWideRow: a longer row is walked by all four waves
 SOLVED, SHARD, EMPTY = 36, (1, 35), 6  # 33 rows with observations in the shard: three batches of 16, the last one a single row
 
 
-def ldl_solve(H, g):
+def ldl_solve(H, g, pivots=None):
+    """pivots: a list that receives d_0 .. d_{n-1} as they are met (tests/test_gpu_implicit_edges.py decides bad rows from them)"""
     n = len(g)
     L, d, z = np.eye(n, dtype=H.dtype), np.zeros(n, H.dtype), g.copy()
     for j in range(n):
         d[j] = H[j, j] - (L[j, :j] * L[j, :j]) @ d[:j]
+        if pivots is not None:
+            pivots.append(d[j])
         for i in range(j + 1, n):
             L[i, j] = (H[i, j] - (L[i, :j] * L[j, :j]) @ d[:j]) / d[j]
         z[j] -= L[j, :j] @ z[:j]

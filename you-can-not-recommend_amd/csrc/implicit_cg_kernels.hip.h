@@ -8,7 +8,8 @@
 //     cgSteps times, unless the row has stopped:
 //         q = op(p);  d = p . q;  rho == 0 or !(d > 0): the row stops, x stays
 //         a = rho / d;  x += a p;  r -= a q;  rho' = r . r;  p = r + (rho' / rho) p;  rho = rho'
-//     store x, rounded once to T; a row whose stored value would not be finite becomes zeros and is counted
+//     store x, rounded once to T; a row that met a rho or d that is not finite (it would stop there and keep its warm start), or
+//     whose stored value would not be finite, becomes zeros and is counted
 // Per application of op a row of n observations costs 2 n k multiply-adds and its share of one k x k x 16 matrix product, where
 // the exact solve costs an n k^2 Gramian and a k^3 / 3 factorisation.
 //
@@ -193,7 +194,7 @@ __global__ __launch_bounds__(256) void implicit_cg_kernel(ImplicitCgArgs<T> a) {
   const int mine = 4 * wave + grp;  // the batch row of this group in the update
   double *xm = xs + mine * ld, *rm = rs + mine * ld, *pm = ps + mine * ld, *qm = qs + mine * ld;
   double rho = 0.0;
-  bool stopped = sStop[mine] != 0;
+  bool stopped = sStop[mine] != 0, poisoned = false;
   for (int it = 0; it <= a.cgSteps; ++it) {
     const bool first = it == 0;
     const double *v = first ? xs : ps;
@@ -223,7 +224,10 @@ __global__ __launch_bounds__(256) void implicit_cg_kernel(ImplicitCgArgs<T> a) {
         d = fma(pv[e], qv[e], d);
       }
       d = implicit_cg_group_sum(d);
-      const bool go = !stopped && rho != 0.0 && d > 0.0;  // (the same in the 16 lanes of a group)
+      // a rho or d that is not finite (NaN / Inf in the row's values, its warm start or G) would stop the row by the rule below
+      // and leave the warm start standing as if it were a result: the row is bad instead
+      if (!stopped && !(isfinite(rho) && isfinite(d))) poisoned = true;
+      const bool go = !stopped && !poisoned && rho != 0.0 && d > 0.0;  // (the same in the 16 lanes of a group)
       const double al = rho / d;
       double rv[NB], s = 0.0;
 #pragma unroll
@@ -247,10 +251,10 @@ __global__ __launch_bounds__(256) void implicit_cg_kernel(ImplicitCgArgs<T> a) {
     }
     __syncthreads();
   }
-  // one rounding to T; a row that would store a value that is not finite becomes zeros and is counted
+  // one rounding to T; a row that met a rho or d that is not finite, or would store a value that is not, becomes zeros and is counted
   const int row = sRow[mine];
   T out[NB];
-  bool bad = false;
+  bool bad = poisoned;
 #pragma unroll
   for (int e = 0; e < NB; ++e) {
     out[e] = (T)xm[l16 + 16 * e];
