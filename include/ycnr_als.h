@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define YCNR_ALS_ABI_VERSION 4 /* 4: + ycnr_als_comm_info, ycnr_als_last_rmse_ms (nothing changed or removed); later, still 4: + ycnr_als_recommend, + ycnr_als_fold_in, ycnr_als_recommend_for_ratings; later, still 4: + ycnr_als_step_implicit; later, still 4: + ycnr_als_step_implicit_cg; later, still 4: + ycnr_als_rank_eval; later, still 4: + ycnr_als_fold_in_implicit, ycnr_als_recommend_for_observations; later, still 4: + ycnr_als_step_implicit_sub */
+#define YCNR_ALS_ABI_VERSION 4 /* 4: + ycnr_als_comm_info, ycnr_als_last_rmse_ms (nothing changed or removed); later, still 4: + ycnr_als_recommend, + ycnr_als_fold_in, ycnr_als_recommend_for_ratings; later, still 4: + ycnr_als_step_implicit; later, still 4: + ycnr_als_step_implicit_cg; later, still 4: + ycnr_als_rank_eval; later, still 4: + ycnr_als_fold_in_implicit, ycnr_als_recommend_for_observations; later, still 4: + ycnr_als_step_implicit_sub; later, still 4: + ycnr_als_fold_in_implicit_wide */
 
 /* error codes */
 #define YCNR_OK 0
@@ -568,7 +568,8 @@ int ycnr_als_step_implicit_cg(ycnr_als *h, int side, double alpha, int32_t cgSte
  *   msOut3    (may be NULL) {G and its reduce, the row kernels, both}
  * For factorsCount <= 128, G is computed by the kernels of ycnr_als_step_implicit and has the bits that entry sees.
  * Refusals as ycnr_als_step_implicit -- except that factorsCount may be up to 512 (beyond: YCNR_ERR_UNSUPPORTED) -- and
- * YCNR_ERR_INVALID for sweeps < 1 or > 16.  The matrices are untouched then.  The fold-in entries below still stop at 128. */
+ * YCNR_ERR_INVALID for sweeps < 1 or > 16.  The matrices are untouched then.  Of the fold-in entries below, ycnr_als_fold_in_implicit_wide serves factorsCount up
+ * to 512; the other two stop at 128. */
 int ycnr_als_step_implicit_sub(ycnr_als *h, int side, double alpha, int32_t sweeps, int32_t *badRows /* may be NULL */,
                                double *msOut3 /* may be NULL */);
 
@@ -600,7 +601,7 @@ int ycnr_als_step_implicit_sub(ycnr_als *h, int side, double alpha, int32_t swee
  *              count of failed rows is not zero.)
  *   msOut3     (may be NULL) {G, its reduce and Linv; the row kernels and the finish; both} from HIP events on the handle's stream
  * YCNR_ERR_INVALID (outputs and matrices untouched): what ycnr_als_fold_in refuses, alpha negative or not finite, unknown flag
- * bits.  YCNR_ERR_UNSUPPORTED: factorsCount > 128 (beyond it only ycnr_als_step_implicit_sub trains the implicit model; there is no fold-in).  nRows == 0 is YCNR_OK.
+ * bits.  YCNR_ERR_UNSUPPORTED: factorsCount > 128 (beyond it ycnr_als_step_implicit_sub trains the implicit model and ycnr_als_fold_in_implicit_wide, below, folds in).  nRows == 0 is YCNR_OK.
  * Enqueued on the handle's stream behind the half-steps in flight, returns with the results on the host; the device buffers stay
  * with the handle (a second call of the same size allocates nothing).  LOCAL, not collective.
  *
@@ -615,6 +616,39 @@ int ycnr_als_recommend_for_observations(ycnr_als *h, double alpha, int64_t nUser
                                         const void *obsVals, const int64_t *skipPtr, const int32_t *skipIds, double globalAvgShift,
                                         double minRecommendRating, int32_t limit, int32_t flags, int32_t *outIds, double *outPredict,
                                         int32_t *outCount, void *outRows /* may be NULL */, int32_t *outStatus, double *deviceMs);
+
+/* ---- Fold-in for the implicit model up to 512 factors ------------------------------------------------
+ *
+ * ycnr_als_step_implicit_sub trains the implicit model up to factorsCount = 512; this entry gives such a model rows for new
+ * users / new items (and serves newcomers of 33 .. 128 observations in dual form below 128 factors, where the entry above sends
+ * them to the exact k x k solve).  The reference has no such operation (lib/emf/Emf.js trains the explicit model only); the row
+ * is the one ycnr_als_fold_in_implicit documents:
+ *     M = Y^T Y + lambda I = L L^T,   Linv = L^-1            once per call, float64 (lambda PLAIN)
+ *     P = Linv Y_S^T (k x n);   K = P^T P;   D = diag(sqrt(alpha r));   c = 1 + alpha r
+ *     (I + D K D) y = D K c;    v = c - D y;    x = Linv^T (Linv (Y_S^T v)),   rounded once to the handle's type
+ * EVERY served row goes this dual way: a row is served if it has 1 .. 128 observations and every value has r >= 0 (a NaN fails
+ * this).  There is no n <= factorsCount condition: I + D K D is symmetric with eigenvalues >= 1 for any n.  M is factorised in
+ * 64-column blocks into images in device memory, and a row streams over the block rows of Linv; nothing on chip grows with
+ * factorsCount^2 (csrc/foldin_wide_kernels.hip.h).  All arithmetic is float64 for both handle types.  Every sum's order is fixed
+ * by (the fixed side's row count, the row) alone: a row's bits do not depend on what else the request holds, on the grid, or on
+ * which of the kernel's two launch classes (<= 32 observations, <= 128) it ran in.  G is recomputed in every call -- by the
+ * Gramian kernels ycnr_als_step_implicit_sub uses for this factorsCount -- and nothing is cached between calls.
+ *   side, alpha, rowPtr, indx, vals, storeIds, outRows, msOut3   as for ycnr_als_fold_in_implicit
+ *   outStatus  per row: 0 solved; 1 a pivot p with !(p > 0), in the row's small system or in M -- and then for EVERY served row of
+ *              the call: zeros, not stored; 2 no observations: zeros; YCNR_FOLD_NOT_SERVED (3): the row has more than 128
+ *              observations or a value with !(r >= 0): zeros, nothing stored.  A non-zero status is NOT an error return.
+ *              What the caller can still do with a row of status 3: for factorsCount <= 128, ycnr_als_fold_in_implicit solves it
+ *              exactly; above 128, add the row to its side with ycnr_als_set_ratings and train it (ycnr_als_step_implicit_sub).
+ * ycnr_als_recommend_for_observations is NOT extended beyond 128 factors: fold in with storeIds, then call ycnr_als_recommend
+ * for the stored users.
+ * YCNR_ERR_INVALID (outputs and matrices untouched): what ycnr_als_fold_in refuses, alpha negative or not finite.
+ * YCNR_ERR_UNSUPPORTED: factorsCount > 512.  nRows == 0 is YCNR_OK.
+ * Enqueued on the handle's stream behind the half-steps in flight, returns with the results on the host; the device buffers stay
+ * with the handle (a second call of the same size allocates nothing).  LOCAL, not collective. */
+#define YCNR_FOLD_NOT_SERVED 3 /* outStatus of ycnr_als_fold_in_implicit_wide: more than 128 observations, or a value with !(r >= 0) */
+int ycnr_als_fold_in_implicit_wide(ycnr_als *h, int side, double alpha, int64_t nRows, const int64_t *rowPtr, const int32_t *indx,
+                                   const void *vals, const int32_t *storeIds /* may be NULL */, void *outRows, int32_t *outStatus,
+                                   double *msOut3 /* may be NULL: {G + factor, rows, total} */);
 
 /* ---- Ranking evaluation: where the model places held-out items -------------------------------------
  *

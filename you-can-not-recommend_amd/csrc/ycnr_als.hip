@@ -20,6 +20,7 @@
 #include "rank_kernels.hip.h"
 #include "foldin_kernels.hip.h"
 #include "foldin_implicit_kernels.hip.h"
+#include "foldin_wide_kernels.hip.h"
 #include "implicit_kernels.hip.h"
 #include "implicit_cg_kernels.hip.h"
 #include "implicit_sub_kernels.hip.h"
@@ -824,6 +825,9 @@ struct ycnr_als {
          // ycnr_als_fold_in_implicit / ycnr_als_recommend_for_observations: L^-1 of G + lambda I, the dual rows, {bad rows, bad factor}
          // (the request, the solved rows and the primal units go through the FOLD_* buffers above)
          FOLD_LINV, FOLD_DUAL, FOLD_FLAGS,
+         // ycnr_als_fold_in_implicit_wide: the images M = G + lambda I (worked on in place) and L; Linv, the served rows and the
+         // flags go through the three buffers above
+         FOLD_WIDE_M, FOLD_WIDE_L,
          // ycnr_als_rank_eval: the slots, the held-out ids, a batch's histogram image, target order and skip marks, the two outputs
          RANK_SLOTS, RANK_TEST, RANK_HIST, RANK_ORDER, RANK_MARK, RANK_OUT, RANK_CAND, REC_NBUF };
   GrowBuf<ExactAlloc> rec[REC_NBUF];
@@ -839,6 +843,7 @@ struct ycnr_als {
   PiecePlan foldPlan;  // ycnr_als_fold_in beyond 128 factors: the plan whose lists are being copied to the device
   FoldCut foldCut;     // ycnr_als_fold_in_implicit: the lists of the request being copied to the device (foldin_plan.h)
   Event foldEv;        // ... and the event between its shared part (G, L^-1) and its rows
+  FoldWideCut foldWideCut;  // ycnr_als_fold_in_implicit_wide: the same for its lists (foldin_wide_plan.h)
   DevPtr<ErrInfo> dErr;
   // The error record is never reset on the device: its count only grows, the host remembers what it has seen
   // (errSeen) and gets the record through an 8-byte copy into page-locked memory at the end of every half-step
@@ -3076,6 +3081,115 @@ int fold_implicit_enqueue_any(ycnr_als *h, int side, double alpha, int64_t nRows
   return h->opt.dtype == YCNR_F64 ? fold_implicit_enqueue<double>(h, side, alpha, nRows, rowPtr, indx, vals, storeIds, flags)
                                   : fold_implicit_enqueue<float>(h, side, alpha, nRows, rowPtr, indx, vals, storeIds, flags);
 }
+
+// ---- implicit fold-in up to 512 factors (foldin_wide_kernels.hip.h, foldin_wide_plan.h) ----
+
+// Uploads the (validated) request and enqueues G -> its reduce (exactly as implicit_sub_enqueue obtains G) -> M -> the blocked
+// factorisation and inverse -> the served rows in their two launch classes -> finish on the handle's stream; recEv[0] in front of
+// the kernels, foldEv behind the part every row shares.  Afterwards FOLD_ROWS / FOLD_STATUS hold the result on the device.
+template <typename T>
+int fold_wide_enqueue(ycnr_als *h, int side, double alpha, int64_t nRows, const int64_t *rowPtr, const int32_t *indx, const void *vals,
+                      const int32_t *storeIds) {
+  typedef ycnr_als A;
+  ycnr_als::Implicit &I = h->implicit;
+  const int k = h->opt.factorsCount, nb = (k + 15) / 16, kp = nb * 16, nt = tile_count(nb);
+  const bool wide = k > kImplicitMaxK;
+  const int nPairs = tile_count((k + 63) / 64), ld = fold_wide_image_ld(k), nb64 = ld / kFoldWideBlock;
+  const int64_t total = rowPtr[nRows];
+  const int64_t m = h->rows(1 - side), sliceRows = wide ? implicit_wide_slice_rows(m) : implicit_slice_rows(m),
+                nSlices = (m + sliceRows - 1) / sliceRows;
+  const double lambda = side == YCNR_BY_USER ? h->opt.userFactReg : h->opt.itemFactReg;
+  const T *fixed = (const T *)h->factors[1 - side];
+  FoldWideCut &cut = h->foldWideCut;  // (kept on the handle: its lists are the source of the copies below)
+  fold_wide_cut<T>(nRows, rowPtr, (const T *)vals, cut);
+  const size_t nShort = cut.shortRows.size(), nLong = cut.longRows.size(), nServed = nShort + nLong;
+  HIP_TRY(h->rec[A::FOLD_PTR].reserve((size_t)(nRows + 1) * 8));
+  HIP_TRY(h->rec[A::FOLD_INDX].reserve(std::max<size_t>((size_t)total * 4 + 64, 8)));
+  HIP_TRY(h->rec[A::FOLD_VALS].reserve(std::max<size_t>((size_t)total * sizeof(T) + 64, 8)));
+  HIP_TRY(h->rec[A::FOLD_ROWS].reserve((size_t)nRows * k * sizeof(T)));
+  HIP_TRY(h->rec[A::FOLD_STATUS].reserve((size_t)nRows * 4));
+  if (storeIds) HIP_TRY(h->rec[A::FOLD_STORE].reserve((size_t)nRows * 4));
+  HIP_TRY(h->rec[A::FOLD_LINV].reserve(fold_wide_image_bytes(k)));
+  HIP_TRY(h->rec[A::FOLD_WIDE_M].reserve(fold_wide_image_bytes(k)));
+  HIP_TRY(h->rec[A::FOLD_WIDE_L].reserve(fold_wide_image_bytes(k)));
+  HIP_TRY(h->rec[A::FOLD_DUAL].reserve(std::max<size_t>(nServed, 1) * 4));
+  HIP_TRY(h->rec[A::FOLD_FLAGS].reserve(2 * sizeof(int32_t)));
+  HIP_TRY(I.gram.reserve((size_t)kp * kp * sizeof(double)));
+  HIP_TRY(I.partial.reserve((size_t)nSlices * (wide ? (size_t)nPairs * 4096 : (size_t)nt * 256) * sizeof(double)));
+  for (Event &ev : h->recEv)
+    if (!ev) HIP_TRY(hipEventCreate(ev.put()));
+  if (!h->foldEv) HIP_TRY(hipEventCreate(h->foldEv.put()));
+  const size_t shortLds = fold_wide_lds_bytes(kFoldWideShortObs, k), longLds = fold_wide_lds_bytes(kFoldWideMaxObs, k);
+  if (int rc = set_max_lds(reinterpret_cast<const void *>(foldin_implicit_wide_kernel<T>), longLds)) return rc;
+  // everything below is enqueued on the handle's stream: behind the half-steps in flight, like ycnr_als_fold_in_implicit
+  int32_t *list = (int32_t *)h->rec[A::FOLD_DUAL].get();
+  HIP_TRY(hipMemcpyAsync(h->rec[A::FOLD_PTR].get(), rowPtr, (size_t)(nRows + 1) * 8, hipMemcpyHostToDevice, h->stream));
+  if (total) {
+    HIP_TRY(hipMemcpyAsync(h->rec[A::FOLD_INDX].get(), indx, (size_t)total * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->rec[A::FOLD_VALS].get(), vals, (size_t)total * sizeof(T), hipMemcpyHostToDevice, h->stream));
+  }
+  if (storeIds) HIP_TRY(hipMemcpyAsync(h->rec[A::FOLD_STORE].get(), storeIds, (size_t)nRows * 4, hipMemcpyHostToDevice, h->stream));
+  if (nShort) HIP_TRY(hipMemcpyAsync(list, cut.shortRows.data(), nShort * 4, hipMemcpyHostToDevice, h->stream));
+  if (nLong) HIP_TRY(hipMemcpyAsync(list + nShort, cut.longRows.data(), nLong * 4, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemsetAsync(h->rec[A::FOLD_STATUS].get(), 0xff, (size_t)nRows * 4, h->stream));  // -1: the row kernel has not solved the row
+  HIP_TRY(hipMemsetAsync(h->rec[A::FOLD_FLAGS].get(), 0, 2 * sizeof(int32_t), h->stream));
+  HIP_TRY(hipEventRecord(h->recEv[0].get(), h->stream));
+  double *G = (double *)I.gram.get(), *partial = (double *)I.partial.get(), *Linv = (double *)h->rec[A::FOLD_LINV].get(),
+         *M = (double *)h->rec[A::FOLD_WIDE_M].get(), *L = (double *)h->rec[A::FOLD_WIDE_L].get();
+  int32_t *devFlags = (int32_t *)h->rec[A::FOLD_FLAGS].get();
+  if (wide) {
+    hipLaunchKernelGGL(implicit_gram_wide_kernel<T>, dim3((unsigned)nPairs, (unsigned)nSlices), dim3(256), 0, h->stream, fixed, m, k, sliceRows, partial);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(implicit_gram_wide_reduce_kernel, dim3((unsigned)nPairs * 16), dim3(256), 0, h->stream, (const double *)partial, (int)nSlices, k, G,
+                       devFlags);
+  } else {
+    const bool vec = k % (int)(16 / sizeof(T)) == 0 && (reinterpret_cast<uintptr_t>(fixed) & 15) == 0;
+    const size_t gramLds = implicit_gram_lds_bytes(k);
+    if (vec)
+      hipLaunchKernelGGL((implicit_gram_kernel<T, true>), dim3((unsigned)nSlices), dim3(256), gramLds, h->stream, fixed, m, k, sliceRows, partial);
+    else
+      hipLaunchKernelGGL((implicit_gram_kernel<T, false>), dim3((unsigned)nSlices), dim3(256), gramLds, h->stream, fixed, m, k, sliceRows, partial);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(implicit_gram_reduce_kernel, dim3((unsigned)nt), dim3(256), 0, h->stream, (const double *)partial, (int)nSlices, k, G, devFlags);
+  }
+  HIP_TRY(hipGetLastError());
+  if (nServed) {  // (without served rows nothing reads Linv, and flags[1] stays 0)
+    hipLaunchKernelGGL(foldin_wide_init_kernel, dim3((unsigned)(ld * ld / 256)), dim3(256), 0, h->stream, (const double *)G, lambda, k, M);
+    HIP_TRY(hipGetLastError());
+    for (int j = 0; j < nb64; ++j) {
+      hipLaunchKernelGGL(foldin_wide_diag_kernel, dim3(1), dim3(256), 0, h->stream, (const double *)M, ld, j, L, Linv, devFlags);
+      HIP_TRY(hipGetLastError());
+      const int below = nb64 - 1 - j;
+      if (!below) break;
+      hipLaunchKernelGGL(foldin_wide_panel_kernel, dim3((unsigned)below), dim3(256), 0, h->stream, (const double *)M, (const double *)Linv, ld, j, L);
+      HIP_TRY(hipGetLastError());
+      hipLaunchKernelGGL(foldin_wide_trail_kernel, dim3((unsigned)tile_count(below)), dim3(256), 0, h->stream, (const double *)L, ld, j, nb64, M);
+      HIP_TRY(hipGetLastError());
+    }
+    for (int d = 1; d < nb64; ++d) {
+      hipLaunchKernelGGL(foldin_wide_inverse_kernel, dim3((unsigned)(nb64 - d)), dim3(256), 0, h->stream, (const double *)L, Linv, ld, d);
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  HIP_TRY(hipEventRecord(h->foldEv.get(), h->stream));
+  T *rows = (T *)h->rec[A::FOLD_ROWS].get();
+  int32_t *status = (int32_t *)h->rec[A::FOLD_STATUS].get();
+  FoldWideArgs<T> w{list, (const int64_t *)h->rec[A::FOLD_PTR].get(), (const int32_t *)h->rec[A::FOLD_INDX].get(), (const T *)h->rec[A::FOLD_VALS].get(),
+                    fixed, (const double *)Linv, rows, status, alpha, k, ld};
+  if (nShort) {
+    hipLaunchKernelGGL(foldin_implicit_wide_kernel<T>, dim3((unsigned)nShort), dim3(kFoldWideThreads), shortLds, h->stream, w);
+    HIP_TRY(hipGetLastError());
+  }
+  if (nLong) {
+    w.rows = list + nShort;
+    hipLaunchKernelGGL(foldin_implicit_wide_kernel<T>, dim3((unsigned)nLong), dim3(kFoldWideThreads), longLds, h->stream, w);
+    HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(foldin_wide_finish_kernel<T>, dim3((unsigned)nRows), dim3(256), 0, h->stream, (const int64_t *)h->rec[A::FOLD_PTR].get(),
+                     (const int32_t *)devFlags, k, rows, status, storeIds ? (T *)h->factors[side] : nullptr, (const int32_t *)h->rec[A::FOLD_STORE].get());
+  HIP_TRY(hipGetLastError());
+  return YCNR_OK;
+}
 }  // namespace
 }  // extern "C++"
 
@@ -3165,6 +3279,39 @@ int ycnr_als_fold_in_implicit(ycnr_als *h, int side, double alpha, int64_t nRows
   if (int rc = fold_check("ycnr_als_fold_in_implicit", h, side, nRows, rowPtr, indx, vals, storeIds)) return rc;
   HIP_TRY(hipSetDevice(h->opt.device));
   if (int rc = fold_implicit_enqueue_any(h, side, alpha, nRows, rowPtr, indx, vals, storeIds, flags)) return rc;
+  typedef ycnr_als A;
+  HIP_TRY(hipEventRecord(h->recEv[1].get(), h->stream));
+  HIP_TRY(hipMemcpyAsync(outRows, h->rec[A::FOLD_ROWS].get(), (size_t)nRows * h->opt.factorsCount * h->ts(), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(outStatus, h->rec[A::FOLD_STATUS].get(), (size_t)nRows * 4, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (msOut3) {
+    float g = 0, r = 0, t = 0;
+    HIP_TRY(hipEventElapsedTime(&g, h->recEv[0].get(), h->foldEv.get()));
+    HIP_TRY(hipEventElapsedTime(&r, h->foldEv.get(), h->recEv[1].get()));
+    HIP_TRY(hipEventElapsedTime(&t, h->recEv[0].get(), h->recEv[1].get()));
+    msOut3[0] = g, msOut3[1] = r, msOut3[2] = t;
+  }
+  return YCNR_OK;
+}
+
+int ycnr_als_fold_in_implicit_wide(ycnr_als *h, int side, double alpha, int64_t nRows, const int64_t *rowPtr, const int32_t *indx, const void *vals,
+                                   const int32_t *storeIds, void *outRows, int32_t *outStatus, double *msOut3) {
+  const char *who = "ycnr_als_fold_in_implicit_wide";
+  if (!h) return fail(YCNR_ERR_INVALID, "null handle");
+  if (side != YCNR_BY_USER && side != YCNR_BY_ITEM) return fail(YCNR_ERR_INVALID, "bad side %d", side);
+  if (nRows < 0 || nRows > 0x7fffffffLL) return fail(YCNR_ERR_INVALID, "%s: bad nRows", who);
+  if (!(alpha >= 0.0) || !std::isfinite(alpha)) return fail(YCNR_ERR_INVALID, "%s: alpha must be finite and >= 0", who);
+  if (h->opt.factorsCount > kFoldWideMaxK) return fail(YCNR_ERR_UNSUPPORTED, "%s: factorsCount %d > %d", who, h->opt.factorsCount, kFoldWideMaxK);
+  if (nRows == 0) {
+    if (msOut3) msOut3[0] = msOut3[1] = msOut3[2] = 0.0;
+    return YCNR_OK;
+  }
+  if (!outRows || !outStatus) return fail(YCNR_ERR_INVALID, "%s: null argument", who);
+  if (int rc = fold_check(who, h, side, nRows, rowPtr, indx, vals, storeIds)) return rc;
+  HIP_TRY(hipSetDevice(h->opt.device));
+  if (int rc = h->opt.dtype == YCNR_F64 ? fold_wide_enqueue<double>(h, side, alpha, nRows, rowPtr, indx, vals, storeIds)
+                                        : fold_wide_enqueue<float>(h, side, alpha, nRows, rowPtr, indx, vals, storeIds))
+    return rc;
   typedef ycnr_als A;
   HIP_TRY(hipEventRecord(h->recEv[1].get(), h->stream));
   HIP_TRY(hipMemcpyAsync(outRows, h->rec[A::FOLD_ROWS].get(), (size_t)nRows * h->opt.factorsCount * h->ts(), hipMemcpyDeviceToHost, h->stream));

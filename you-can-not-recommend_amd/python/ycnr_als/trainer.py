@@ -492,6 +492,24 @@ class AlsDevice:
                                                 ms.ctypes.data))
         return rows, status, ms
 
+    def fold_in_implicit_wide(self, side, alpha, rowPtr, indx, vals, storeIds=None):
+        """fold_in_implicit() for models of up to 512 factors (ycnr_als_fold_in_implicit_wide): every row of 1 .. 128 non-negative
+        observations is solved in dual form from one blocked factorisation of G + lambda I per call.  Returns (rows [n x k],
+        status [n]: 0 solved / 1 bad pivot / 2 no observations / 3 not served (more than 128 observations or a negative value),
+        ms = np.array([G and factor, rows, total]))."""
+        rp, ix, vl = self._request_csr(rowPtr, indx, vals)
+        n = len(rp) - 1
+        st = None if storeIds is None else np.ascontiguousarray(storeIds, np.int32).reshape(-1)
+        if st is not None and len(st) != n:
+            raise ValueError("storeIds needs one id per request row")
+        rows = np.zeros((n, self.k), self.dtype)
+        status = np.zeros(n, np.int32)
+        ms = np.zeros(3, np.float64)
+        check(self._L.ycnr_als_fold_in_implicit_wide(self._h, SIDES[side], float(alpha), n, rp.ctypes.data, ix.ctypes.data if len(ix) else None,
+                                                     vl.ctypes.data if len(vl) else None, None if st is None else st.ctypes.data,
+                                                     rows.ctypes.data, status.ctypes.data, ms.ctypes.data))
+        return rows, status, ms
+
     def recommend_for_observations(self, alpha, obsPtr, obsIds, obsVals, skipPtr, skipIds, globalAvgShift=0.0, minRecommendRating=7.0,
                                    limit=20, primal_only=False):
         """fold_in_implicit('byUser', alpha) of the request's observations, then recommend() on the solved rows without a host
