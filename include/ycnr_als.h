@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define YCNR_ALS_ABI_VERSION 4 /* 4: + ycnr_als_comm_info, ycnr_als_last_rmse_ms (nothing changed or removed); later, still 4: + ycnr_als_recommend, + ycnr_als_fold_in, ycnr_als_recommend_for_ratings; later, still 4: + ycnr_als_step_implicit; later, still 4: + ycnr_als_step_implicit_cg; later, still 4: + ycnr_als_rank_eval; later, still 4: + ycnr_als_fold_in_implicit, ycnr_als_recommend_for_observations; later, still 4: + ycnr_als_step_implicit_sub; later, still 4: + ycnr_als_fold_in_implicit_wide */
+#define YCNR_ALS_ABI_VERSION 4 /* 4: + ycnr_als_comm_info, ycnr_als_last_rmse_ms (nothing changed or removed); later, still 4: + ycnr_als_recommend, + ycnr_als_fold_in, ycnr_als_recommend_for_ratings; later, still 4: + ycnr_als_step_implicit; later, still 4: + ycnr_als_step_implicit_cg; later, still 4: + ycnr_als_rank_eval; later, still 4: + ycnr_als_fold_in_implicit, ycnr_als_recommend_for_observations; later, still 4: + ycnr_als_step_implicit_sub; later, still 4: + ycnr_als_fold_in_implicit_wide; later, still 4: + ycnr_als_step_implicit_wide */
 
 /* error codes */
 #define YCNR_OK 0
@@ -542,7 +542,7 @@ int ycnr_als_step_implicit_cg(ycnr_als *h, int side, double alpha, int32_t cgSte
 
 /* The same half-step by 16-wide subspace solves, factorsCount <= 512: block coordinate descent on each row's quadratic, the
  * subspace solver of iALS++ (Rendle, Krichene, Zhang, Koren 2021), warm-started from the row as it stands in the handle.  The
- * way to train the implicit model beyond 128 factors, where a row's k x k image no longer fits on chip: the method's state per
+ * cheap way to train the implicit model beyond 128 factors (the exact one: ycnr_als_step_implicit_wide), where a row's k x k image no longer fits on chip: the method's state per
  * row is one k-vector and the largest system it solves is 16 x 16 (csrc/implicit_sub_kernels.hip.h).
  * Notation is that of ycnr_als_step_implicit:
  * - Y = all m rows of the fixed matrix, G = Y^T Y, lambda plain.
@@ -649,6 +649,31 @@ int ycnr_als_recommend_for_observations(ycnr_als *h, double alpha, int64_t nUser
 int ycnr_als_fold_in_implicit_wide(ycnr_als *h, int side, double alpha, int64_t nRows, const int64_t *rowPtr, const int32_t *indx,
                                    const void *vals, const int32_t *storeIds /* may be NULL */, void *outRows, int32_t *outStatus,
                                    double *msOut3 /* may be NULL: {G + factor, rows, total} */);
+
+/* ---- The exact implicit half-step up to 512 factors ----------------------------------------------------
+ *
+ * ycnr_als_step_implicit for factorsCount 1 .. 512: the same A_u, b_u and x_u (lambda PLAIN), solved exactly, for both handle
+ * types.  Beyond 128 factors a row's k x k image fits no LDS, so the rows go two ways, and which way depends on the row alone:
+ *   - a row of 1 .. 128 observations with every value r >= 0 is exactly a row ycnr_als_fold_in_implicit_wide serves.  It is
+ *     solved in that entry's dual form by that entry's kernels (G by the Gramian kernels ycnr_als_step_implicit_sub uses for this
+ *     factorsCount, M = G + lambda I factorised once per call), reading the side's resident ratings and writing into the side's
+ *     matrix: its bits are the bits that entry returns for the same observations on the same handle;
+ *   - every other non-empty row -- more than 128 observations, or a value with !(r >= 0), a NaN included -- is solved in primal
+ *     form (csrc/implicit_wide_kernels.hip.h): its weighted Gramian in the handle's precision on the MFMA, chunk by chunk
+ *     (options.chunkRatings, else 4096) into slabs in device memory; the slabs added in slab order in float64, + G + lambda I; a
+ *     blocked Cholesky factorisation of the packed-tile image in device memory on the float64 MFMA; one rounding at the store.
+ *     The rows go through in batches whose slabs fit a fixed arena (384 MB), whatever the size of the shard.
+ * Rows of the shard without observations become zeros, rows outside it are untouched, the result is written in place, and the
+ * call is synchronous on the handle's stream.  Every sum's order is fixed by (the fixed side's row count, the row, the chunk
+ * length): a row's bits depend neither on the grid, nor on its batch, nor on what else the side holds.
+ *   badRows  rows that became zeros: a primal row with a pivot p with !(p > 0) or a result that is not finite; a dual row whose
+ *            small system has such a pivot; and, after a bad pivot of M itself, EVERY non-empty row of the shard.  Still YCNR_OK.
+ *   msOut3   {G, its reduce and the factorisation of M; the row kernels; both}, milliseconds.
+ * Refusals as ycnr_als_step_implicit_sub: YCNR_ERR_UNSUPPORTED for factorsCount > 512, a communicator of several ranks, a banded
+ * side or a side uploaded in several pieces; YCNR_ERR_STATE without ratings or with half-steps in flight; YCNR_ERR_INVALID for
+ * a null handle, a bad side, alpha negative or not finite.  The matrices are untouched then.  The first call after an upload
+ * reads the side's values once on the device to cut its rows (and synchronises the stream for it). */
+int ycnr_als_step_implicit_wide(ycnr_als *h, int side, double alpha, int32_t *badRows /* may be NULL */, double *msOut3 /* may be NULL */);
 
 /* ---- Ranking evaluation: where the model places held-out items -------------------------------------
  *

@@ -24,6 +24,7 @@
 #include "implicit_kernels.hip.h"
 #include "implicit_cg_kernels.hip.h"
 #include "implicit_sub_kernels.hip.h"
+#include "implicit_wide_kernels.hip.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -728,6 +729,19 @@ struct ImplicitSubPlan {
   DevPtr<Unit> dRows;
   DevPtr<int32_t> dEmpty;
 };
+// ... and that of ycnr_als_step_implicit_wide (implicit_wide_plan.h): rows are local to the piece.  Which rows are dual needs the
+// values, which live on the device: implicit_wide_classify_kernel reads them once, when the plan is built.
+struct ImplicitWidePlan {
+  bool built = false;
+  int64_t nShort = 0, nLong = 0, nEmpty = 0, maxBatchSlabs = 0;
+  DevPtr<int64_t> dPtr;     // the piece's row pointer from 0
+  DevPtr<int32_t> dDual;    // the short class, then the long one
+  DevPtr<int32_t> dStatus;  // a word per row of the piece: what the dual row kernel reports
+  DevPtr<int32_t> dEmpty;
+  DevPtr<Unit> dUnits;
+  DevPtr<SplitRow> dRows;
+  std::vector<ImplicitWideBatch> batches;
+};
 
 struct Part {
   Ratings R;
@@ -735,6 +749,7 @@ struct Part {
   std::vector<int64_t> hostPtr;  // the piece's row pointer as uploaded (8 bytes per row): what ImplicitPlan is built from
   ImplicitPlan implicit;
   ImplicitSubPlan implicitSub;
+  ImplicitWidePlan implicitWide;
   Event ev[5], ready, x0, x1;
   // fork / join of the piece's dual-class launches on the handle's side streams, and "all kernels of the piece done":
   // per piece, because two pieces are in flight at a time (on the handle's two piece streams)
@@ -836,6 +851,7 @@ struct ycnr_als {
   // allocates nothing), the bad-row count and the three timing events; scores: ycnr_als_step_implicit_sub, a double per rating
   struct Implicit {
     GrowBuf<ExactAlloc> gram, partial, slabs, scores;
+    GrowBuf<ExactAlloc> wideArena;  // ycnr_als_step_implicit_wide: the slabs and row images of a batch of primal rows
     DevPtr<int32_t> dBad;
     HostPtr<int32_t> hBad;
     Event ev[3];
@@ -3084,6 +3100,74 @@ int fold_implicit_enqueue_any(ycnr_als *h, int side, double alpha, int64_t nRows
 
 // ---- implicit fold-in up to 512 factors (foldin_wide_kernels.hip.h, foldin_wide_plan.h) ----
 
+// What ycnr_als_fold_in_implicit_wide and ycnr_als_step_implicit_wide share: G, the images M, L and Linv, and the two flags.
+int fold_wide_factor_reserve(ycnr_als *h, int side) {
+  typedef ycnr_als A;
+  ycnr_als::Implicit &I = h->implicit;
+  const int k = h->opt.factorsCount, nb = (k + 15) / 16, kp = nb * 16, nt = tile_count(nb), nPairs = tile_count((k + 63) / 64);
+  const bool wide = k > kImplicitMaxK;
+  const int64_t m = h->rows(1 - side), sliceRows = wide ? implicit_wide_slice_rows(m) : implicit_slice_rows(m),
+                nSlices = (m + sliceRows - 1) / sliceRows;
+  HIP_TRY(h->rec[A::FOLD_LINV].reserve(fold_wide_image_bytes(k)));
+  HIP_TRY(h->rec[A::FOLD_WIDE_M].reserve(fold_wide_image_bytes(k)));
+  HIP_TRY(h->rec[A::FOLD_WIDE_L].reserve(fold_wide_image_bytes(k)));
+  HIP_TRY(h->rec[A::FOLD_FLAGS].reserve(2 * sizeof(int32_t)));
+  HIP_TRY(I.gram.reserve((size_t)kp * kp * sizeof(double)));
+  HIP_TRY(I.partial.reserve((size_t)nSlices * (wide ? (size_t)nPairs * 4096 : (size_t)nt * 256) * sizeof(double)));
+  return YCNR_OK;
+}
+// G -> its reduce (exactly as implicit_sub_enqueue obtains G; the reduce clears *gramFlag) and, if `factor`, M -> the blocked
+// factorisation -> Linv on the handle's stream.  A bad pivot of M raises flags[1] of FOLD_FLAGS, which the caller has cleared.
+template <typename T>
+int fold_wide_factor_enqueue(ycnr_als *h, int side, int32_t *gramFlag, bool factor) {
+  typedef ycnr_als A;
+  ycnr_als::Implicit &I = h->implicit;
+  const int k = h->opt.factorsCount, nb = (k + 15) / 16, nt = tile_count(nb);
+  const bool wide = k > kImplicitMaxK;
+  const int nPairs = tile_count((k + 63) / 64), ld = fold_wide_image_ld(k), nb64 = ld / kFoldWideBlock;
+  const int64_t m = h->rows(1 - side), sliceRows = wide ? implicit_wide_slice_rows(m) : implicit_slice_rows(m),
+                nSlices = (m + sliceRows - 1) / sliceRows;
+  const double lambda = side == YCNR_BY_USER ? h->opt.userFactReg : h->opt.itemFactReg;
+  const T *fixed = (const T *)h->factors[1 - side];
+  double *G = (double *)I.gram.get(), *partial = (double *)I.partial.get(), *Linv = (double *)h->rec[A::FOLD_LINV].get(),
+         *M = (double *)h->rec[A::FOLD_WIDE_M].get(), *L = (double *)h->rec[A::FOLD_WIDE_L].get();
+  int32_t *devFlags = (int32_t *)h->rec[A::FOLD_FLAGS].get();
+  if (wide) {
+    hipLaunchKernelGGL(implicit_gram_wide_kernel<T>, dim3((unsigned)nPairs, (unsigned)nSlices), dim3(256), 0, h->stream, fixed, m, k, sliceRows, partial);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(implicit_gram_wide_reduce_kernel, dim3((unsigned)nPairs * 16), dim3(256), 0, h->stream, (const double *)partial, (int)nSlices, k, G,
+                       gramFlag);
+  } else {
+    const bool vec = k % (int)(16 / sizeof(T)) == 0 && (reinterpret_cast<uintptr_t>(fixed) & 15) == 0;
+    const size_t gramLds = implicit_gram_lds_bytes(k);
+    if (vec)
+      hipLaunchKernelGGL((implicit_gram_kernel<T, true>), dim3((unsigned)nSlices), dim3(256), gramLds, h->stream, fixed, m, k, sliceRows, partial);
+    else
+      hipLaunchKernelGGL((implicit_gram_kernel<T, false>), dim3((unsigned)nSlices), dim3(256), gramLds, h->stream, fixed, m, k, sliceRows, partial);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(implicit_gram_reduce_kernel, dim3((unsigned)nt), dim3(256), 0, h->stream, (const double *)partial, (int)nSlices, k, G, gramFlag);
+  }
+  HIP_TRY(hipGetLastError());
+  if (!factor) return YCNR_OK;
+  hipLaunchKernelGGL(foldin_wide_init_kernel, dim3((unsigned)(ld * ld / 256)), dim3(256), 0, h->stream, (const double *)G, lambda, k, M);
+  HIP_TRY(hipGetLastError());
+  for (int j = 0; j < nb64; ++j) {
+    hipLaunchKernelGGL(foldin_wide_diag_kernel, dim3(1), dim3(256), 0, h->stream, (const double *)M, ld, j, L, Linv, devFlags);
+    HIP_TRY(hipGetLastError());
+    const int below = nb64 - 1 - j;
+    if (!below) break;
+    hipLaunchKernelGGL(foldin_wide_panel_kernel, dim3((unsigned)below), dim3(256), 0, h->stream, (const double *)M, (const double *)Linv, ld, j, L);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(foldin_wide_trail_kernel, dim3((unsigned)tile_count(below)), dim3(256), 0, h->stream, (const double *)L, ld, j, nb64, M);
+    HIP_TRY(hipGetLastError());
+  }
+  for (int d = 1; d < nb64; ++d) {
+    hipLaunchKernelGGL(foldin_wide_inverse_kernel, dim3((unsigned)(nb64 - d)), dim3(256), 0, h->stream, (const double *)L, Linv, ld, d);
+    HIP_TRY(hipGetLastError());
+  }
+  return YCNR_OK;
+}
+
 // Uploads the (validated) request and enqueues G -> its reduce (exactly as implicit_sub_enqueue obtains G) -> M -> the blocked
 // factorisation and inverse -> the served rows in their two launch classes -> finish on the handle's stream; recEv[0] in front of
 // the kernels, foldEv behind the part every row shares.  Afterwards FOLD_ROWS / FOLD_STATUS hold the result on the device.
@@ -3091,14 +3175,8 @@ template <typename T>
 int fold_wide_enqueue(ycnr_als *h, int side, double alpha, int64_t nRows, const int64_t *rowPtr, const int32_t *indx, const void *vals,
                       const int32_t *storeIds) {
   typedef ycnr_als A;
-  ycnr_als::Implicit &I = h->implicit;
-  const int k = h->opt.factorsCount, nb = (k + 15) / 16, kp = nb * 16, nt = tile_count(nb);
-  const bool wide = k > kImplicitMaxK;
-  const int nPairs = tile_count((k + 63) / 64), ld = fold_wide_image_ld(k), nb64 = ld / kFoldWideBlock;
+  const int k = h->opt.factorsCount, ld = fold_wide_image_ld(k);
   const int64_t total = rowPtr[nRows];
-  const int64_t m = h->rows(1 - side), sliceRows = wide ? implicit_wide_slice_rows(m) : implicit_slice_rows(m),
-                nSlices = (m + sliceRows - 1) / sliceRows;
-  const double lambda = side == YCNR_BY_USER ? h->opt.userFactReg : h->opt.itemFactReg;
   const T *fixed = (const T *)h->factors[1 - side];
   FoldWideCut &cut = h->foldWideCut;  // (kept on the handle: its lists are the source of the copies below)
   fold_wide_cut<T>(nRows, rowPtr, (const T *)vals, cut);
@@ -3109,13 +3187,8 @@ int fold_wide_enqueue(ycnr_als *h, int side, double alpha, int64_t nRows, const 
   HIP_TRY(h->rec[A::FOLD_ROWS].reserve((size_t)nRows * k * sizeof(T)));
   HIP_TRY(h->rec[A::FOLD_STATUS].reserve((size_t)nRows * 4));
   if (storeIds) HIP_TRY(h->rec[A::FOLD_STORE].reserve((size_t)nRows * 4));
-  HIP_TRY(h->rec[A::FOLD_LINV].reserve(fold_wide_image_bytes(k)));
-  HIP_TRY(h->rec[A::FOLD_WIDE_M].reserve(fold_wide_image_bytes(k)));
-  HIP_TRY(h->rec[A::FOLD_WIDE_L].reserve(fold_wide_image_bytes(k)));
   HIP_TRY(h->rec[A::FOLD_DUAL].reserve(std::max<size_t>(nServed, 1) * 4));
-  HIP_TRY(h->rec[A::FOLD_FLAGS].reserve(2 * sizeof(int32_t)));
-  HIP_TRY(I.gram.reserve((size_t)kp * kp * sizeof(double)));
-  HIP_TRY(I.partial.reserve((size_t)nSlices * (wide ? (size_t)nPairs * 4096 : (size_t)nt * 256) * sizeof(double)));
+  if (int rc = fold_wide_factor_reserve(h, side)) return rc;
   for (Event &ev : h->recEv)
     if (!ev) HIP_TRY(hipEventCreate(ev.put()));
   if (!h->foldEv) HIP_TRY(hipEventCreate(h->foldEv.put()));
@@ -3134,43 +3207,10 @@ int fold_wide_enqueue(ycnr_als *h, int side, double alpha, int64_t nRows, const 
   HIP_TRY(hipMemsetAsync(h->rec[A::FOLD_STATUS].get(), 0xff, (size_t)nRows * 4, h->stream));  // -1: the row kernel has not solved the row
   HIP_TRY(hipMemsetAsync(h->rec[A::FOLD_FLAGS].get(), 0, 2 * sizeof(int32_t), h->stream));
   HIP_TRY(hipEventRecord(h->recEv[0].get(), h->stream));
-  double *G = (double *)I.gram.get(), *partial = (double *)I.partial.get(), *Linv = (double *)h->rec[A::FOLD_LINV].get(),
-         *M = (double *)h->rec[A::FOLD_WIDE_M].get(), *L = (double *)h->rec[A::FOLD_WIDE_L].get();
+  const double *Linv = (const double *)h->rec[A::FOLD_LINV].get();
   int32_t *devFlags = (int32_t *)h->rec[A::FOLD_FLAGS].get();
-  if (wide) {
-    hipLaunchKernelGGL(implicit_gram_wide_kernel<T>, dim3((unsigned)nPairs, (unsigned)nSlices), dim3(256), 0, h->stream, fixed, m, k, sliceRows, partial);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(implicit_gram_wide_reduce_kernel, dim3((unsigned)nPairs * 16), dim3(256), 0, h->stream, (const double *)partial, (int)nSlices, k, G,
-                       devFlags);
-  } else {
-    const bool vec = k % (int)(16 / sizeof(T)) == 0 && (reinterpret_cast<uintptr_t>(fixed) & 15) == 0;
-    const size_t gramLds = implicit_gram_lds_bytes(k);
-    if (vec)
-      hipLaunchKernelGGL((implicit_gram_kernel<T, true>), dim3((unsigned)nSlices), dim3(256), gramLds, h->stream, fixed, m, k, sliceRows, partial);
-    else
-      hipLaunchKernelGGL((implicit_gram_kernel<T, false>), dim3((unsigned)nSlices), dim3(256), gramLds, h->stream, fixed, m, k, sliceRows, partial);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(implicit_gram_reduce_kernel, dim3((unsigned)nt), dim3(256), 0, h->stream, (const double *)partial, (int)nSlices, k, G, devFlags);
-  }
-  HIP_TRY(hipGetLastError());
-  if (nServed) {  // (without served rows nothing reads Linv, and flags[1] stays 0)
-    hipLaunchKernelGGL(foldin_wide_init_kernel, dim3((unsigned)(ld * ld / 256)), dim3(256), 0, h->stream, (const double *)G, lambda, k, M);
-    HIP_TRY(hipGetLastError());
-    for (int j = 0; j < nb64; ++j) {
-      hipLaunchKernelGGL(foldin_wide_diag_kernel, dim3(1), dim3(256), 0, h->stream, (const double *)M, ld, j, L, Linv, devFlags);
-      HIP_TRY(hipGetLastError());
-      const int below = nb64 - 1 - j;
-      if (!below) break;
-      hipLaunchKernelGGL(foldin_wide_panel_kernel, dim3((unsigned)below), dim3(256), 0, h->stream, (const double *)M, (const double *)Linv, ld, j, L);
-      HIP_TRY(hipGetLastError());
-      hipLaunchKernelGGL(foldin_wide_trail_kernel, dim3((unsigned)tile_count(below)), dim3(256), 0, h->stream, (const double *)L, ld, j, nb64, M);
-      HIP_TRY(hipGetLastError());
-    }
-    for (int d = 1; d < nb64; ++d) {
-      hipLaunchKernelGGL(foldin_wide_inverse_kernel, dim3((unsigned)(nb64 - d)), dim3(256), 0, h->stream, (const double *)L, Linv, ld, d);
-      HIP_TRY(hipGetLastError());
-    }
-  }
+  // (without served rows nothing reads Linv, and flags[1] stays 0)
+  if (int rc = fold_wide_factor_enqueue<T>(h, side, devFlags, nServed != 0)) return rc;
   HIP_TRY(hipEventRecord(h->foldEv.get(), h->stream));
   T *rows = (T *)h->rec[A::FOLD_ROWS].get();
   int32_t *status = (int32_t *)h->rec[A::FOLD_STATUS].get();
@@ -3188,6 +3228,124 @@ int fold_wide_enqueue(ycnr_als *h, int side, double alpha, int64_t nRows, const 
   hipLaunchKernelGGL(foldin_wide_finish_kernel<T>, dim3((unsigned)nRows), dim3(256), 0, h->stream, (const int64_t *)h->rec[A::FOLD_PTR].get(),
                      (const int32_t *)devFlags, k, rows, status, storeIds ? (T *)h->factors[side] : nullptr, (const int32_t *)h->rec[A::FOLD_STORE].get());
   HIP_TRY(hipGetLastError());
+  return YCNR_OK;
+}
+
+// ---- the exact implicit half-step up to 512 factors (implicit_wide_kernels.hip.h, implicit_wide_plan.h) ----
+
+// bytes of its slab arena (YCNR_IMPLICIT_WIDE_ARENA_MB, read when a piece's plan is built: experiments force several batches)
+int64_t implicit_wide_arena_bytes() {
+  if (const char *e = getenv("YCNR_IMPLICIT_WIDE_ARENA_MB")) return (int64_t)std::max(1, atoi(e)) << 20;
+  return kImplicitWideArenaBytes;
+}
+
+// The cut of the piece (implicit_wide_plan.h) and its lists on the device.  Synchronises the handle's stream once.
+template <typename T>
+int implicit_wide_build_plan(ycnr_als *h, Part &part) {
+  ImplicitWidePlan N;
+  const int k = h->opt.factorsCount;
+  const int64_t nRows = part.R.rowEnd - part.R.rowBegin;
+  std::vector<int64_t> ptr((size_t)nRows + 1, 0);
+  for (int64_t r = 1; r <= nRows; ++r) ptr[(size_t)r] = part.hostPtr[(size_t)r] - part.hostPtr[0];
+  std::vector<uint8_t> nonNegative((size_t)nRows, 0);
+  HIP_TRY(hipMalloc(N.dPtr.put(), sizeof(int64_t) * ptr.size()));
+  HIP_TRY(hipMemcpy(N.dPtr.get(), ptr.data(), sizeof(int64_t) * ptr.size(), hipMemcpyHostToDevice));
+  if (nRows) {
+    DevPtr<uint8_t> dNonNegative;
+    HIP_TRY(hipMalloc(dNonNegative.put(), (size_t)nRows));
+    hipLaunchKernelGGL(implicit_wide_classify_kernel<T>, dim3((unsigned)((nRows + 255) / 256)), dim3(256), 0, h->stream, (const int64_t *)N.dPtr.get(),
+                       (const T *)part.R.dVals.get(), nRows, dNonNegative.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(nonNegative.data(), dNonNegative.get(), (size_t)nRows, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMalloc(N.dStatus.put(), sizeof(int32_t) * (size_t)nRows));
+  }
+  ImplicitWideCut cut;
+  implicit_wide_cut(ptr.data(), nRows, nonNegative.data(), h->autoChunk ? kImplicitChunk : h->opt.chunkRatings,
+                    wide_arena_slabs(k, implicit_wide_arena_bytes()), cut);
+  N.nShort = (int64_t)cut.dualShort.size(), N.nLong = (int64_t)cut.dualLong.size(), N.nEmpty = (int64_t)cut.empty.size();
+  if (N.nShort + N.nLong) {
+    HIP_TRY(hipMalloc(N.dDual.put(), sizeof(int32_t) * (size_t)(N.nShort + N.nLong)));
+    if (N.nShort) HIP_TRY(hipMemcpy(N.dDual.get(), cut.dualShort.data(), sizeof(int32_t) * (size_t)N.nShort, hipMemcpyHostToDevice));
+    if (N.nLong) HIP_TRY(hipMemcpy(N.dDual.get() + N.nShort, cut.dualLong.data(), sizeof(int32_t) * (size_t)N.nLong, hipMemcpyHostToDevice));
+  }
+  if (N.nEmpty) {
+    HIP_TRY(hipMalloc(N.dEmpty.put(), sizeof(int32_t) * cut.empty.size()));
+    HIP_TRY(hipMemcpy(N.dEmpty.get(), cut.empty.data(), sizeof(int32_t) * cut.empty.size(), hipMemcpyHostToDevice));
+  }
+  if (!cut.rows.empty()) {
+    HIP_TRY(hipMalloc(N.dUnits.put(), sizeof(Unit) * cut.units.size()));
+    HIP_TRY(hipMemcpy(N.dUnits.get(), cut.units.data(), sizeof(Unit) * cut.units.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMalloc(N.dRows.put(), sizeof(SplitRow) * cut.rows.size()));
+    HIP_TRY(hipMemcpy(N.dRows.get(), cut.rows.data(), sizeof(SplitRow) * cut.rows.size(), hipMemcpyHostToDevice));
+  }
+  for (const ImplicitWideBatch &b : cut.batches) N.maxBatchSlabs = std::max(N.maxBatchSlabs, b.nUnits);
+  N.batches = std::move(cut.batches);
+  N.built = true;
+  part.implicitWide = std::move(N);
+  return YCNR_OK;
+}
+
+// G -> its reduce -> M, L, Linv (fold_wide_factor_enqueue) -> the dual rows in the two launch classes of the fold-in, reading the
+// side's resident CSR and writing into the side's matrix -> their count -> the primal rows batch by batch (Gramian, then solve)
+// -> zero rows, all on the handle's stream
+template <typename T>
+int implicit_wide_enqueue(ycnr_als *h, int side, Part &part, double alpha) {
+  typedef ycnr_als A;
+  ycnr_als::Implicit &I = h->implicit;
+  const ImplicitWidePlan &P = part.implicitWide;
+  const int k = h->opt.factorsCount, ld = fold_wide_image_ld(k), nsq = wide_squares(k);
+  const T *fixed = (const T *)h->factors[1 - side];
+  T *solved = (T *)h->factors[side] + part.R.rowBegin * k;  // the kernels count rows from the piece's first
+  const double lambda = side == YCNR_BY_USER ? h->opt.userFactReg : h->opt.itemFactReg;
+  if (int rc = fold_wide_factor_reserve(h, side)) return rc;
+  if (P.maxBatchSlabs) HIP_TRY(I.wideArena.reserve((size_t)P.maxBatchSlabs * (size_t)wide_slab_elems(k) * sizeof(double)));
+  if (!I.dBad) HIP_TRY(hipMalloc(I.dBad.put(), sizeof(int32_t)));
+  if (!I.hBad) HIP_TRY(hipHostMalloc((void **)I.hBad.put(), sizeof(int32_t), hipHostMallocDefault));
+  for (Event &e : I.ev)
+    if (!e) HIP_TRY(hipEventCreate(e.put()));
+  const size_t shortLds = fold_wide_lds_bytes(kFoldWideShortObs, k), longLds = fold_wide_lds_bytes(kFoldWideMaxObs, k),
+               gramLds = wide_gram_lds_bytes(sizeof(T)), solveLds = wide_solve_lds_bytes(k);
+  if (int rc = set_max_lds(reinterpret_cast<const void *>(foldin_implicit_wide_kernel<T>), longLds)) return rc;
+  if (int rc = set_max_lds(reinterpret_cast<const void *>(implicit_wide_gram_kernel<T>), gramLds)) return rc;
+  if (int rc = set_max_lds(reinterpret_cast<const void *>(implicit_wide_solve_kernel<T>), solveLds)) return rc;
+  int32_t *devFlags = (int32_t *)h->rec[A::FOLD_FLAGS].get();
+  HIP_TRY(hipMemsetAsync(devFlags, 0, 2 * sizeof(int32_t), h->stream));
+  HIP_TRY(hipEventRecord(I.ev[0].get(), h->stream));
+  if (int rc = fold_wide_factor_enqueue<T>(h, side, I.dBad.get(), true)) return rc;  // (M is factored whatever the rows: its bad pivot fails every row)
+  HIP_TRY(hipEventRecord(I.ev[1].get(), h->stream));
+  const double *Linv = (const double *)h->rec[A::FOLD_LINV].get();
+  FoldWideArgs<T> w{P.dDual.get(), P.dPtr.get(), part.R.dIndx.get(), (const T *)part.R.dVals.get(), fixed, Linv, solved, P.dStatus.get(), alpha, k, ld};
+  if (P.nShort) {
+    hipLaunchKernelGGL(foldin_implicit_wide_kernel<T>, dim3((unsigned)P.nShort), dim3(kFoldWideThreads), shortLds, h->stream, w);
+    HIP_TRY(hipGetLastError());
+  }
+  if (P.nLong) {
+    w.rows = P.dDual.get() + P.nShort;
+    hipLaunchKernelGGL(foldin_implicit_wide_kernel<T>, dim3((unsigned)P.nLong), dim3(kFoldWideThreads), longLds, h->stream, w);
+    HIP_TRY(hipGetLastError());
+  }
+  if (P.nShort + P.nLong) {
+    hipLaunchKernelGGL(implicit_wide_dual_finish_kernel<T>, dim3((unsigned)((P.nShort + P.nLong + 255) / 256)), dim3(256), 0, h->stream,
+                       (const int32_t *)P.dDual.get(), P.nShort + P.nLong, (const int32_t *)P.dStatus.get(), (const int32_t *)devFlags, k, solved,
+                       I.dBad.get());
+    HIP_TRY(hipGetLastError());
+  }
+  for (const ImplicitWideBatch &b : P.batches) {
+    ImplicitWideArgs<T> a{P.dUnits.get() + b.unit0, P.dRows.get() + b.row0, part.R.dIndx.get(), (const T *)part.R.dVals.get(), fixed, solved,
+                          (const double *)I.gram.get(), (double *)I.wideArena.get(), (const int32_t *)devFlags, I.dBad.get(), alpha, lambda, k};
+    hipLaunchKernelGGL(implicit_wide_gram_kernel<T>, dim3((unsigned)(b.nUnits * nsq)), dim3(256), gramLds, h->stream, a);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(implicit_wide_solve_kernel<T>, dim3((unsigned)b.nRows), dim3(kWideSolveThreads), solveLds, h->stream, a);
+    HIP_TRY(hipGetLastError());
+  }
+  if (P.nEmpty) {
+    hipLaunchKernelGGL(implicit_zero_rows_kernel<T>, dim3((unsigned)((P.nEmpty * k + 255) / 256)), dim3(256), 0, h->stream,
+                       (const int32_t *)P.dEmpty.get(), P.nEmpty, k, solved);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipEventRecord(I.ev[2].get(), h->stream));
+  HIP_TRY(hipMemcpyAsync(I.hBad.get(), I.dBad.get(), sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
   return YCNR_OK;
 }
 }  // namespace
@@ -3322,6 +3480,36 @@ int ycnr_als_fold_in_implicit_wide(ycnr_als *h, int side, double alpha, int64_t 
     HIP_TRY(hipEventElapsedTime(&g, h->recEv[0].get(), h->foldEv.get()));
     HIP_TRY(hipEventElapsedTime(&r, h->foldEv.get(), h->recEv[1].get()));
     HIP_TRY(hipEventElapsedTime(&t, h->recEv[0].get(), h->recEv[1].get()));
+    msOut3[0] = g, msOut3[1] = r, msOut3[2] = t;
+  }
+  return YCNR_OK;
+}
+
+int ycnr_als_step_implicit_wide(ycnr_als *h, int side, double alpha, int32_t *badRows, double *msOut3) {
+  const char *who = "ycnr_als_step_implicit_wide";
+  if (!h) return fail(YCNR_ERR_INVALID, "null handle");
+  if (side != YCNR_BY_USER && side != YCNR_BY_ITEM) return fail(YCNR_ERR_INVALID, "bad side %d", side);
+  if (!(alpha >= 0.0) || !std::isfinite(alpha)) return fail(YCNR_ERR_INVALID, "%s: alpha must be finite and >= 0", who);
+  if (h->opt.factorsCount > kImplicitWideMaxK) return fail(YCNR_ERR_UNSUPPORTED, "%s: factorsCount %d > %d", who, h->opt.factorsCount, kImplicitWideMaxK);
+  std::vector<Part> &parts = h->parts[side];
+  if (parts.empty()) return fail(YCNR_ERR_STATE, "%s: set_ratings was not called for this side", who);
+  if (h->infoPending) return fail(YCNR_ERR_STATE, "%s: half-steps are in flight (ycnr_als_sync first)", who);
+  if (h->comm.active() && h->comm.world > 1) return fail(YCNR_ERR_UNSUPPORTED, "%s: not with a communicator of several ranks", who);
+  if (h->banded[side].on) return fail(YCNR_ERR_UNSUPPORTED, "%s: not for a banded side", who);
+  if (parts.size() != 1) return fail(YCNR_ERR_UNSUPPORTED, "%s: the side was uploaded in %zu pieces", who, parts.size());
+  HIP_TRY(hipSetDevice(h->opt.device));
+  Part &part = parts[0];
+  const bool f64 = h->opt.dtype == YCNR_F64;
+  if (!part.implicitWide.built)
+    if (int rc = f64 ? implicit_wide_build_plan<double>(h, part) : implicit_wide_build_plan<float>(h, part)) return rc;
+  if (int rc = f64 ? implicit_wide_enqueue<double>(h, side, part, alpha) : implicit_wide_enqueue<float>(h, side, part, alpha)) return rc;
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (badRows) *badRows = *h->implicit.hBad.get();
+  if (msOut3) {
+    float g = 0, r = 0, t = 0;
+    HIP_TRY(hipEventElapsedTime(&g, h->implicit.ev[0].get(), h->implicit.ev[1].get()));
+    HIP_TRY(hipEventElapsedTime(&r, h->implicit.ev[1].get(), h->implicit.ev[2].get()));
+    HIP_TRY(hipEventElapsedTime(&t, h->implicit.ev[0].get(), h->implicit.ev[2].get()));
     msOut3[0] = g, msOut3[1] = r, msOut3[2] = t;
   }
   return YCNR_OK;

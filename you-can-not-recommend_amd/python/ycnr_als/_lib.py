@@ -54,7 +54,7 @@ EXPORTS = [
     "ycnr_als_comm_info", "ycnr_als_last_rmse_ms", "ycnr_als_set_ratings_banded", "ycnr_als_defer_exchange",
     "ycnr_als_step_implicit", "ycnr_als_step_implicit_cg", "ycnr_als_rank_eval",
     "ycnr_als_fold_in_implicit", "ycnr_als_recommend_for_observations", "ycnr_als_step_implicit_sub",
-    "ycnr_als_fold_in_implicit_wide",
+    "ycnr_als_fold_in_implicit_wide", "ycnr_als_step_implicit_wide",
 ]
 FOLD_PRIMAL_ONLY = 1  # YCNR_FOLD_PRIMAL_ONLY
 FOLD_NOT_SERVED = 3  # YCNR_FOLD_NOT_SERVED
@@ -184,6 +184,8 @@ def load():
     L.ycnr_als_fold_in_implicit.argtypes = [vp, i32, dbl, i64, vp, vp, vp, vp, i32, vp, vp, vp]
     L.ycnr_als_fold_in_implicit_wide.restype = i32
     L.ycnr_als_fold_in_implicit_wide.argtypes = [vp, i32, dbl, i64, vp, vp, vp, vp, vp, vp, vp]
+    L.ycnr_als_step_implicit_wide.restype = i32
+    L.ycnr_als_step_implicit_wide.argtypes = [vp, i32, dbl, C.POINTER(C.c_int32), vp]
     L.ycnr_als_recommend_for_observations.restype = i32
     L.ycnr_als_recommend_for_observations.argtypes = [vp, dbl, i64, vp, vp, vp, vp, vp, dbl, dbl, i32, i32, vp, vp, vp, vp, vp, C.POINTER(dbl)]
     L.ycnr_csr_transpose.restype = i32

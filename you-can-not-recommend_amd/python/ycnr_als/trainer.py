@@ -344,6 +344,15 @@ class AlsDevice:
             check(self._L.ycnr_als_step_implicit_cg(self._h, SIDES[side], float(alpha), int(cg_steps), C.byref(bad), ms.ctypes.data))
         return bad.value, ms
 
+    def step_implicit_wide(self, side, alpha):
+        """step_implicit(side, alpha) solved exactly for models of up to 512 factors (ycnr_als_step_implicit_wide): rows of
+        1 .. 128 non-negative observations in the dual form of fold_in_implicit_wide -- with that call's bits --, every other
+        non-empty row by a blocked factorisation of its k x k image in device memory.  Returns (badRows, ms) as step_implicit."""
+        bad = C.c_int32(0)
+        ms = np.zeros(3, np.float64)
+        check(self._L.ycnr_als_step_implicit_wide(self._h, SIDES[side], float(alpha), C.byref(bad), ms.ctypes.data))
+        return bad.value, ms
+
     def step_async(self, side):
         check(self._L.ycnr_als_step_async(self._h, SIDES[side]))
 
